@@ -5,18 +5,25 @@ One "step" = one complete SIPP::prove (sipp/src/lib.rs:42-106: statement hash, a
 two pairing products + Fiat-Shamir + two folds) over a synthetic statement of n random-looking G1 x G2 pairs,
 called the way SURVEY.md section 8(d) defines the metric: `ripp_sipp_prove` on HOST slices (the statement in host
 memory; the upload happens inside the call, the statement hash starts on the caller's buffers before it).
-`value` = n / t_step (pairs per second, whole job).  `value_resident` is the same proof from a statement already
-resident in HBM (ripp_sipp_job_prove), timed over the same number of steps right after.
+`value` = n / t_step (pairs per second, whole job).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--log-n 20]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--log-n 20] [--dump-outputs DIR] [--full [--cpu-log-n 20]]
   N > 1:  python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
           (one rank per GPU, RCCL; STRONG scaling: n is fixed, shards are index residues mod N; the step is
            ripp_sipp_prove_sharded on every rank's host shard)
 
-Extra objects on the JSON line: "roofline" (dominant kernel, algorithmic HBM bytes / measured launch time vs the
-8 TB/s peak -- this path is integer-ALU bound, see DESIGN.md -- with the multiply-adds the kernel executes against the
-hardware's issue rate under "int_alu") and "cpu_baseline" (the CPU oracle = a C/OpenMP restatement of the reference
-algorithm, timed on this box's host cores AT THE HEADLINE SIZE; rank 0, N = 1 only).
+A plain run sets up, warms up, times the K steps and prints the JSON line; everything on it comes from those steps, e.g. "roofline"
+(dominant kernel, algorithmic HBM bytes / measured launch time vs the 8 TB/s peak -- this path is integer-ALU bound, see DESIGN.md --
+with the multiply-adds the kernel executes against the hardware's issue rate under "int_alu").
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed call returned: DIR/proof.npy (the 2 log2 n GT elements,
+2 log2 n x 144) and DIR/challenges.npy (log2 n x 8), float64, each 64-bit word as its two 32-bit halves (low first) -- exact, so two
+builds can be compared element for element.  The statement is the same synthetic one in every run.
+
+--full adds what takes runs of its own: "value_resident" (the same proof from a statement already resident in HBM, ripp_sipp_job_prove,
+timed over the same number of steps), the configs 2 and 3 figures (N = 1, n = 2^20) and "cpu_baseline" (the CPU oracle = a C/OpenMP
+restatement of the reference algorithm, timed on this box's host cores AT THE HEADLINE SIZE, its proof compared with the GPU's; rank 0,
+N = 1 only, --cpu-log-n 0 disables it).
 """
 import argparse
 import json
@@ -63,7 +70,8 @@ def self_launch(args):
         sk.bind(("127.0.0.1", 0)); port = sk.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.abspath(__file__), "--gpus", str(args.gpus), "--steps", str(args.steps), "--warmup", str(args.warmup),
-           "--log-n", str(args.log_n), "--cpu-log-n", str(args.cpu_log_n)]
+           "--log-n", str(args.log_n), "--cpu-log-n", str(args.cpu_log_n)] + (["--full"] if args.full else []) + \
+          (["--dump-outputs", os.path.abspath(args.dump_outputs)] if args.dump_outputs else [])
     env = dict(os.environ); env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0"); env.setdefault("OMP_NUM_THREADS", "1")
     p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, text=True)
     line = None
@@ -163,8 +171,12 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--log-n", type=int, default=20)
-    ap.add_argument("--cpu-log-n", type=int, default=20, help="log2 size of the CPU-baseline run (default: the headline size, ~85 s on 16 CPUs; 0 disables)")
+    ap.add_argument("--cpu-log-n", type=int, default=20, help="with --full: log2 size of the CPU-baseline run (default: the headline size, ~85 s on 16 CPUs; 0 disables)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's proof and challenges to DIR/*.npy (float64, exact 32-bit halves)")
+    ap.add_argument("--full", action="store_true", help="also time the resident-statement proof, the configs 2 and 3 and the CPU baseline")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     rank = int(os.environ.get("RANK", "0")); world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -260,6 +272,7 @@ def main():
     # ---- the timed region: the section 8(d) call.  HOST slices in, proof bytes out; upload of the statement (shard) inside the call
     kill_rank = int(os.environ.get("RIPP_BENCH_KILL_RANK", "-1"))       # test hook (tests/test_sharded_gloo.py): this rank kills itself in round 3 of its second proof
     host_calls = [0]
+    last_ch = [None]
 
     def host_step():
         host_calls[0] += 1
@@ -272,6 +285,7 @@ def main():
             proof, ch, st = R.SIPP.prove_one_shot(a, b, r, value)       # ripp_sipp_prove: hashing starts on the caller's buffers, overlaps the upload and the first kernels
         else:
             proof, ch, st = native_sipp_prove(a, b, r, value, full=full if rank == 0 else None)      # ripp_sipp_prove_sharded
+        last_ch[0] = ch
         return proof, st
     total, times, stats_all, ref_proof = timed(host_step, args.warmup, args.steps, None)
     ms_per_step = total / args.steps * 1e3
@@ -279,18 +293,25 @@ def main():
     stats = stats_all[-1]
     hash_ms_steps = [st["statement_hash_ms"] + st["statement_hash_wait_ms"] for st in stats_all]        # THIS call's hash, per step (rank 0)
 
-    # ---- the same proof from a statement (shard) already resident in HBM: ripp_sipp_job_prove[_sharded]; same number of steps
-    job = R.SippJob(a, b, r, rank=rank, world=world)
+    if args.dump_outputs and rank == 0:
+        # the caller's arrays of the last timed call (every timed proof equals it: timed() asserts so), u64 words as exact u32 halves in float64
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in (("proof", ref_proof), ("challenges", last_ch[0])):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), np.ascontiguousarray(arr, dtype=np.uint64).view(np.uint32).astype(np.float64))
 
-    def resident_step():
-        if world == 1:
-            proof, ch, st = job.prove(value)
-        else:
-            proof, ch, st = native_sipp_job_prove(job, value, full=full if rank == 0 else None)
-        return proof, st
-    total_res, times_res, stats_res, _ = timed(resident_step, 1, args.steps, ref_proof)
-    resident_ms = total_res / args.steps * 1e3
-    job.close(); job = None
+    if args.full:
+        # ---- the same proof from a statement (shard) already resident in HBM: ripp_sipp_job_prove[_sharded]; same number of steps
+        job = R.SippJob(a, b, r, rank=rank, world=world)
+
+        def resident_step():
+            if world == 1:
+                proof, ch, st = job.prove(value)
+            else:
+                proof, ch, st = native_sipp_job_prove(job, value, full=full if rank == 0 else None)
+            return proof, st
+        total_res, times_res, stats_res, _ = timed(resident_step, 1, args.steps, ref_proof)
+        resident_ms = total_res / args.steps * 1e3
+        job.close(); job = None
 
     if rank == 0:
         # dominant kernel of the path on this rank, from HIP events recorded on the engine's own stream
@@ -333,7 +354,6 @@ def main():
             # the hash of the SAME calls, step by step: a slow step is a slow hash (the core's clock / a neighbour on its L3), not a slow GPU -- read the two lists side by side
             "statement_hash_ms_all": [round(h, 3) for h in hash_ms_steps],
             "post_hash_ms_all": [round(t * 1e3 - h, 3) for t, h in zip(times, hash_ms_steps)],
-            "value_resident": n / (resident_ms * 1e-3), "ms_per_step_resident": resident_ms,
             # `bound` / `achieved` / `peak` / `frac` are the byte roofline the bench contract asks for; `binding` names the roof that actually limits the kernel
             "roofline": {"bound": "hbm", "binding": "int_alu", "kernel": dom[3], "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
@@ -367,16 +387,18 @@ def main():
         # AFTER the digest exists: post_hash_ms = step - duration of the statement hash OF THE SAME CALLS (ripp_stats.statement_hash_ms, averaged
         # over the timed steps; DESIGN.md section 6 has the model).
         out["post_hash_ms"] = ms_per_step - hash_ms
-        out["post_hash_ms_resident"] = resident_ms - sum(st["statement_hash_ms"] + st["statement_hash_wait_ms"] for st in stats_res) / len(stats_res)
         out["look_ahead"] = {"items": int(stats["look_items"]), "pairs": int(stats["look_pairs"]), "order": "(1,l) (1,r) (2,l) (2,r) (3,l) (3,r)"}
         out["miller_loops_per_s"] = 2 * (n - 1) / (ms_per_step * 1e-3)            # the 2 (n - 1) Miller loops of the reference's prover per second of the step
-        if world == 1 and args.log_n == 20 and not os.environ.get("RIPP_BENCH_NO_CONFIGS"):
+        if args.full:
+            out["value_resident"] = n / (resident_ms * 1e-3); out["ms_per_step_resident"] = resident_ms
+            out["post_hash_ms_resident"] = resident_ms - sum(st["statement_hash_ms"] + st["statement_hash_wait_ms"] for st in stats_res) / len(stats_res)
+        if args.full and world == 1 and args.log_n == 20 and not os.environ.get("RIPP_BENCH_NO_CONFIGS"):
             out.update(config_figures(R, np, args.cpu_log_n > 0))
         parity_ok = True
-        if world == 1 and args.cpu_log_n > 0:
+        if args.full and world == 1 and args.cpu_log_n > 0:
             cb = cpu_baseline(args.cpu_log_n, (a, b, r, value))
             eproof = cb.pop("_proof")
-            if eproof is not None:          # the CPU baseline ran the oracle's prover on the bench statement: a live full-size parity check in every default run
+            if eproof is not None:          # the CPU baseline ran the oracle's prover on the bench statement: a live full-size parity check in every --full run
                 parity_ok = bool(np.array_equal(eproof, ref_proof))
                 cb["proof_equals_gpu"] = parity_ok
             out["cpu_baseline"] = cb

@@ -6,7 +6,7 @@ Why a fixture: one oracle proof at n = 2^20 costs ~80-110 s of 16 CPUs, and the 
 The fixture is a CACHE of the oracle's output, not a second source of truth:
   * tests/test_gpu_full_size.py compares the GPU proofs with it AND has the oracle's verifier (which re-derives every challenge from its own
     Blake2s of the statement) accept them; RIPP_TEST_LIVE_ORACLE=1 recomputes the oracle's proofs instead of loading them;
-  * bench.py's cpu_baseline leg runs the oracle's prover at n = 2^20 LIVE in every default run and compares its proof with the GPU's.
+  * bench.py's cpu_baseline leg runs the oracle's prover at n = 2^20 LIVE in every `bench.py --full` run and compares its proof with the GPU's.
 Takes ~6 min on 8 cores:  python tests/golden/gen_sipp_2p20_oracle_proofs.py"""
 import os
 import sys

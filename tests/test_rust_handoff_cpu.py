@@ -1,7 +1,8 @@
 """The arkworks hand-off (rust/ripp-hip) cannot be compiled in this image (no Rust toolchain), so what CAN be checked
 mechanically is checked here: the Rust sources name no PRIVATE item of the reference (build round 3's dumpers read `proof.gt_elems`, a
-private field of sipp::Proof -- rustc E0616), and every item they import from the reference crates is declared `pub` there (the second
-check needs /root/reference and is skipped on the GPU box)."""
+private field of sipp::Proof -- rustc E0616), and every item they import from the reference crates is declared `pub` there (checked against
+tests/golden/reference_public_items.json, an index of the reference's public items made by tests/golden/gen_reference_public_items.py)."""
+import json
 import os
 import re
 
@@ -10,7 +11,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RUST = os.path.join(ROOT, "rust", "ripp-hip")
 FILES = ["examples/dump_kat.rs", "examples/dump_kat_377.rs", "src/lib.rs", "src/convert.rs", "src/ffi.rs", "src/fused.rs", "tests/vec_roundtrip.rs"]
-REF = "/root/reference"
+REF_PUBLIC = os.path.join(ROOT, "tests", "golden", "reference_public_items.json")
 
 # fields that are private / pub(crate) in the reference: sipp::Proof (sipp/src/lib.rs:32-34), GIPAProof / GIPAAux (gipa.rs:24-77: pub(crate)),
 # TIPAProof (tipa/mod.rs:41-65), TIPAWithSSMProof (structured_scalar_message.rs:138-156), AggregateProof (groth16_aggregation.rs:59-69)
@@ -54,7 +55,6 @@ def _flatten(prefix, body):
 CRATE_DIR = {"ark_sipp": "sipp", "ark_inner_products": "inner_products", "ark_dh_commitments": "dh_commitments", "ark_ip_proofs": "ip_proofs"}
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="the reference checkout only exists in the build container")
 @pytest.mark.parametrize("rel", FILES)
 def test_every_item_imported_from_the_reference_is_public_there(rel):
     code = strip_comments(open(os.path.join(RUST, rel)).read())
@@ -66,17 +66,17 @@ def test_every_item_imported_from_the_reference_is_public_there(rel):
     for m in re.finditer(r"\b(ark_(?:sipp|inner_products|dh_commitments|ip_proofs))::([A-Za-z_][A-Za-z0-9_]*)\b", code):
         paths.append(m.group(1) + "::" + m.group(2))
     assert paths or rel.endswith(("ffi.rs", "convert.rs", "vec_roundtrip.rs"))
+    with open(REF_PUBLIC) as f:
+        public = json.load(f)
     for path in sorted(set(paths)):
         parts = path.split("::")
-        src_dir = os.path.join(REF, CRATE_DIR[parts[0]], "src")
+        src_dir = CRATE_DIR[parts[0]] + "/src"
         name, mods = parts[-1], parts[1:-1]
         # the file the item lives in: src/<mods...>.rs or src/<mods...>/mod.rs, src/lib.rs for crate-root items
-        cands = [os.path.join(src_dir, *mods) + ".rs", os.path.join(src_dir, *mods, "mod.rs")] if mods else [os.path.join(src_dir, "lib.rs")]
-        files = [c for c in cands if os.path.isfile(c)]
+        cands = ["/".join([src_dir, *mods]) + ".rs", "/".join([src_dir, *mods, "mod.rs"])] if mods else [src_dir + "/lib.rs"]
+        files = [c for c in cands if c in public]
         assert files, f"{rel}: module of `{path}` not found in the reference"
-        text = open(files[0]).read()
-        assert re.search(r"^\s*pub\s+(?:fn|struct|trait|type|enum|mod|const)\s+%s\b" % re.escape(name), text, flags=re.M), \
-            f"{rel}: `{path}` is not a public item of the reference ({files[0]})"
+        assert name in public[files[0]], f"{rel}: `{path}` is not a public item of the reference ({files[0]})"
 
 
 def test_design_does_not_call_the_handoff_compiled():

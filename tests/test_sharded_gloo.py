@@ -757,11 +757,12 @@ def test_sharded_gipa_and_aggregate(engine, orc, tmp_path_factory, world, n, env
 def test_bench_ranks_on_one_device_reports_the_hash_excluded_figures(engine, gpus):
     """`bench.py --gpus 2 / 8` end to end (self-launch through torch.distributed.run, the rank processes on cuda:0, the library's collectives over
     gloo): the JSON line keeps `value` end to end and adds what makes an N > 1 curve readable -- the time rank 0 was blocked on the statement
-    hash, the rest of the step, the hash-excluded rate, the look-ahead the ranks ran in the window, the time in the per-round exchanges."""
+    hash, the rest of the step, the hash-excluded rate, the look-ahead the ranks ran in the window, the time in the per-round exchanges; with
+    --full also the resident-statement figure."""
     import json
     import subprocess
     env = dict(os.environ, RIPP_BENCH_SINGLE_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    p = subprocess.run([sys.executable, os.path.join(os.path.dirname(HERE), "bench.py"), "--gpus", str(gpus), "--steps", "1", "--warmup", "1", "--log-n", "17"], env=env, capture_output=True, text=True, timeout=900)
+    p = subprocess.run([sys.executable, os.path.join(os.path.dirname(HERE), "bench.py"), "--gpus", str(gpus), "--steps", "1", "--warmup", "1", "--log-n", "17", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     line = [ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1]
     out = json.loads(line)

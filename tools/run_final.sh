@@ -6,7 +6,7 @@ bash tools/run_profiles.sh $TAG > gpurun_out/prof_$TAG.log 2>&1
 O=gpurun_out/final_$TAG; mkdir -p $O
 timeout 900 python3 tools/scaling_ipp.py 1 20 $O --cpu-max 12 > $O/scaling_ipp.log 2>&1
 timeout 300 python3 tools/aggregate_bench.py 14 > $O/aggregate_2p14.json 2> $O/aggregate_2p14.err
-for G in 2 4 8; do RIPP_BENCH_SINGLE_DEVICE=1 timeout 600 python3 bench.py --gpus $G --steps 3 --warmup 1 --cpu-log-n 0 > $O/bench_n${G}_single_device_gloo.json 2> $O/bench_n$G.err; done
+for G in 2 4 8; do RIPP_BENCH_SINGLE_DEVICE=1 timeout 600 python3 bench.py --gpus $G --steps 3 --warmup 1 --full --cpu-log-n 0 > $O/bench_n${G}_single_device_gloo.json 2> $O/bench_n$G.err; done
 timeout 900 python3 tools/scaling_ipp.py 4 20 $O/c377 --cpu-max 12 --curve 377 > $O/scaling_ipp_377.log 2>&1
 bash tools/post_hash_timeline.sh 0 450 > $O/post_hash_timeline.txt 2>&1
 # the look-ahead planner priced for a slower device (ripp_config.plan_derate_pct): same box, alternating with the plain plan

@@ -13,7 +13,7 @@ export TMPDIR=/tmp
 ./tools/ubench/build/fqgroup 200 > $OUT/fqgroup.txt 2>&1
 # stage 2a of the pairing product in isolation: k_line_products_q (six-product sums) against k_line_products_k (Karatsuba), bit-compared
 ( ./tools/ubench/build/lpbench 17 2 5; ./tools/ubench/build/lpbench 17 6 3; ./tools/ubench/build/lpbench 15 2 3 ) > $OUT/lpbench.txt 2>&1
-timeout 900 python3 bench.py --steps 5 --warmup 1 > $OUT/bench_n1.json 2> $OUT/bench_n1.err        # incl. the CPU baseline at n = 2^20 (~100 s)
+timeout 900 python3 bench.py --steps 5 --warmup 1 --full > $OUT/bench_n1.json 2> $OUT/bench_n1.err        # incl. the CPU baseline at n = 2^20 (~100 s)
 timeout 300 rocprofv3 --kernel-trace --stats -d $OUT/kstats -o k --output-format csv -- python3 bench.py --steps 3 --warmup 1 --cpu-log-n 0 > $OUT/kstats.log 2>&1
 timeout 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $OUT/pmc_fetch -o f --output-format csv -- python3 bench.py --steps 1 --warmup 0 --cpu-log-n 0 > $OUT/pmc_fetch.log 2>&1
 timeout 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $OUT/pmc_write -o w --output-format csv -- python3 bench.py --steps 1 --warmup 0 --cpu-log-n 0 > $OUT/pmc_write.log 2>&1
