@@ -101,18 +101,30 @@ def test_sipp_prove_vs_oracle(E, o, n):
         assert not E.SIPP.verify(a, b, r, value, bad)
 
 
-def test_sipp_degenerate_statement_vs_oracle(E, o):
-    n = 64
+def _sipp_degenerate(E, o, n):
     a, b, r = o.gen_g1(70, n), o.gen_g2(80, n), o.gen_scalars(9, n)
-    r[1] = 0; a[2] = 0; b[3] = 0; a[n - 1] = 0; b[n - 1] = 0
+    r[1] = 0; r[n // 2] = 0
+    a[2] = 0; b[3] = 0; a[n - 1] = 0; b[n - 1] = 0
     a[5] = a[4]; b[5] = b[4]; r[5] = r[4]
     q = 4 + n // 2
     a[q] = a[4]; b[q] = b[4]; r[q] = r[4]
+    a[6, 6:] = o.fp_to_limbs((o.P - o.limbs_to_fp(a[7, 6:])) % o.P); a[6, :6] = a[7, :6]   # a_6 = -a_7
     value = E.product_of_pairings_with_coeffs(a, b, r)
     assert np.array_equal(value, o.product_of_pairings_with_coeffs(a, b, r))
     proof = E.SIPP.prove(a, b, r, value)
     rc, eproof, _ = o.sipp_prove(a, b, r, value)
     assert rc == 0 and np.array_equal(proof, eproof) and E.SIPP.verify(a, b, r, value, proof)
+
+
+def test_sipp_degenerate_statement_vs_oracle(E, o):
+    """zero coefficients, identities, repeated points (x P + P) and a negated pair (P - P): the proof equals the oracle's"""
+    _sipp_degenerate(E, o, 64)
+
+
+def test_sipp_degenerate_statement_vs_oracle_2p15(E, o):
+    """the same degenerate statement at n = 32768, where round 0 folds G2 with the carry-free 4-lane GLS kernel and its flagged lanes go to
+    k_fold_g2_gls_split_fix (test_gpu_parity.py has the BLS12-381 form)"""
+    _sipp_degenerate(E, o, 1 << 15)
 
 
 def test_both_curves_side_by_side(E, engine, orc, o):
