@@ -36,28 +36,9 @@ def test_vm_layers_are_homogeneous_and_in_bounds(curve):
     bias that fits 16 bits and covers its negative terms (values < 2p for program inputs and products, < 16p for unreduced LIN results),
     and a light LIN result stays below 16 p."""
     import vmgen
+    import vm_model
     for (name, G), c in vmgen.validate().items():
-        assert c["nslots"] <= 255
-        bound = {s: vmgen.BOUND_IN for s in c["ins"].values()}; bound[vmgen.ZERO_SLOT] = 0; bound[vmgen.DUMP_SLOT] = 0
-        for kind, row in c["layers"]:
-            assert kind in (vmgen.MUL, vmgen.LIN) and len(row) == G
-            new = {}
-            heavy_layer = kind == vmgen.LIN and any(op["heavy"] for op in row)
-            for op in row:
-                assert 0 <= op["dst"] < c["nslots"]
-                if kind == vmgen.MUL:
-                    assert all(0 <= a < c["nslots"] for a in op["a"]) and 0 <= op["neg"] < 16
-                    ob = [sum((vmgen.NEG_K if (op["neg"] >> (2 * h + t)) & 1 else bound[op["a"][2 * h + t]]) for t in range(2) if op["a"][2 * h + t] != vmgen.ZERO_SLOT or t == 0) for h in range(2)]
-                    assert all(bound[a] <= vmgen.LIGHT_MAX for a in op["a"]) and ob[0] * ob[1] <= vmgen.VMAX
-                    new[op["dst"]] = 2
-                else:
-                    assert len(op["terms"]) <= vmgen.TMAX and all(abs(cf) <= vmgen.COEF_MAX and 0 <= sl < c["nslots"] for cf, sl in op["terms"]) and 0 <= op["nbias"] < 65536
-                    neg = sum(-cf * bound[sl] for cf, sl in op["terms"] if cf < 0); pos = sum(cf * bound[sl] for cf, sl in op["terms"] if cf > 0)
-                    assert op["nbias"] >= neg and pos + op["nbias"] <= vmgen.HEAVY_MAX
-                    assert heavy_layer or pos + op["nbias"] <= vmgen.LIGHT_MAX
-                    new[op["dst"]] = 2 if heavy_layer else pos + op["nbias"]
-            bound.update(new)
-        for s in c["outs"].values(): assert bound[s] <= vmgen.BOUND_IN          # kernels read outputs back as canonical values
+        vm_model.check_contract(c)                 # the assertions live in tests/vm_model.py, where the model and the device tests use them too
 
 
 def test_kaliski_fix_table():
