@@ -385,6 +385,65 @@ int32_t ripp_tipa_ssm_verify(const ripp_verifier_srs* v_srs, const ripp_gt* com_
 int32_t ripp_verify_aggregate_proof(const ripp_verifier_srs* v_srs, const ripp_groth16_vk* vk, const ripp_fr* public_inputs, size_t n, size_t m,
                                     const ripp_aggregate_proof* proof, int32_t* accept);
 
+/* ---- polynomial commitments -- ip_proofs/src/applications/poly_commit/mod.rs --------------------------------------------------
+ * KZG (mod.rs:50-119), BivariatePolynomialCommitment (:142-296: KZG commitments of the y-polynomials, committed to with AFGHO and opened with
+ * TIPAWithSSM) and UnivariatePolynomialCommitment (:298-388: the sqrt split).  Coefficients are Montgomery Fr limbs, low degree first; a
+ * bivariate polynomial is a row-major matrix, coeffs[i * stride + j] = coefficient j of y_polynomials[i].  Nothing of a commit or an opening
+ * is computed on the host except the powers of x, the Fiat-Shamir hashes and the final exponentiations of the second-tier rounds. */
+/* UnivariatePolynomialCommitment::bivariate_degrees (mod.rs:299-306); host only, needs no device.  degree >= 1. */
+int32_t ripp_pc_univariate_degrees(size_t degree, size_t* x_degree, size_t* y_degree);
+/* Resident SRS: the KZG powers g^{alpha^i}, i <= y_degree (normalised, with the extended form the batched MSM gathers from), the second-tier
+ * SRS over h^{beta^i}, i <= 2 x_degree (SRS { g_alpha_powers: vec![g], .. }, mod.rs:165-170) and the verifier key.  x_degree + 1 must be a
+ * power of two; x_degree = 0 gives a KZG-only handle (KZG::setup, mod.rs:56-76). */
+typedef struct ripp_pc_srs ripp_pc_srs;
+/* BivariatePolynomialCommitment::setup (mod.rs:148-172) with the trapdoors GIVEN (tests fix them; a deployment draws and forgets them): powers computed on the device */
+int32_t ripp_pc_srs_setup(const ripp_fr* alpha, const ripp_fr* beta, size_t x_degree, size_t y_degree, ripp_pc_srs** srs);
+/* the same from caller-supplied powers: kzg_powers[y_degree + 1], h_beta_powers[2 x_degree + 1] */
+int32_t ripp_pc_srs_create(const ripp_g1a* kzg_powers, size_t y_degree, const ripp_g2j* h_beta_powers, size_t x_degree, const ripp_g1j* g_beta, const ripp_g2j* h_alpha, ripp_pc_srs** srs);
+void    ripp_pc_srs_destroy(ripp_pc_srs* srs);
+int32_t ripp_pc_srs_degrees(const ripp_pc_srs* srs, size_t* x_degree, size_t* y_degree);      /* parse_bivariate_degrees_from_srs, mod.rs:308-312 */
+int32_t ripp_pc_srs_verifier_key(const ripp_pc_srs* srs, ripp_verifier_srs* out);             /* SRS::get_verifier_key, tipa/mod.rs:120-127 */
+int32_t ripp_pc_srs_kzg_powers(const ripp_pc_srs* srs, ripp_g1a* out /* [y_degree + 1] */);   /* kzg_srs of mod.rs:161-164 */
+/* out[r] = sum_{i < cols} scalars[r * stride + i] * bases[i], r < rows: `rows` MultiexponentiationInnerProduct::inner_product calls
+ * (inner_products/src/lib.rs:128-141) over ONE base vector -- the y_polynomial_coms loop of mod.rs:188-193 -- as one pipeline over the
+ * rows x windows pairs (the bases are uploaded and extended once).  RIPP_ERR_ARG for cols > n or stride < cols; rows == 0 writes nothing.
+ * Rows are processed in chunks when the scratch of the whole batch would exceed ripp_config.mem_cap_bytes / free memory (the same points);
+ * ripp_msm_batch_chunks: the chunks of the LAST batched MSM of this process (0: the per-row loop, which the legacy switches no_msm_glv /
+ * no_fq / no_vm select). */
+int32_t ripp_msm_g1_batch_a(const ripp_g1a* bases, size_t n, const ripp_fr* scalars, size_t rows, size_t cols, size_t stride, ripp_g1j* out);
+int32_t ripp_msm_batch_chunks(void);
+/* KZG::commit / open / verify (mod.rs:78-88, 90-109, 111-119) on the handle's powers.  Trailing zero coefficients are stripped as DensePolynomial
+ * does; more coefficients than powers is RIPP_ERR_ARG (the reference asserts).  eval (optional) = p(point). */
+int32_t ripp_kzg_commit(const ripp_pc_srs* srs, const ripp_fr* coeffs, size_t len, ripp_g1j* com);
+int32_t ripp_kzg_open(const ripp_pc_srs* srs, const ripp_fr* coeffs, size_t len, const ripp_fr* point, ripp_g1j* proof, ripp_fr* eval);
+int32_t ripp_kzg_verify(const ripp_verifier_srs* v_srs, const ripp_g1j* com, const ripp_fr* point, const ripp_fr* eval, const ripp_g1j* proof, int32_t* accept);
+/* OpeningProof (mod.rs:142-146): ip_proof = the members of ripp_tipa_ssm_prove, step arrays caller-allocated for rounds = log2(x_degree + 1) and filled in
+ * ROUND order; projective members are any representative of the group element. */
+typedef struct {
+    ripp_gt* com_gt;                            /* [rounds][2] */
+    ripp_g1j* com_g1;                           /* [rounds][2] */
+    ripp_fr* transcript;                        /* [rounds] */
+    ripp_g1j base_a; ripp_fr base_b;
+    ripp_g2j final_ck_a; ripp_g2j opening_a;
+    ripp_fr kzg_challenge;
+    ripp_g1j y_eval_comm, kzg_proof;
+} ripp_pc_opening;
+/* BivariatePolynomialCommitment::commit (mod.rs:174-196): rows <= x_degree + 1 (missing rows are zero polynomials), cols <= y_degree + 1, stride >= cols.
+ * One batched MSM gives y_coms[x_degree + 1]; com is their AFGHO commitment under the even h_beta powers. */
+int32_t ripp_pc_commit(const ripp_pc_srs* srs, const ripp_fr* coeffs, size_t rows, size_t cols, size_t stride, ripp_gt* com, ripp_g1j* y_coms);
+/* BivariatePolynomialCommitment::open (mod.rs:198-263) at (x, y); eval (optional) = p(x, y).  x_degree >= 1 (RIPP_ERR_POW2 otherwise). */
+int32_t ripp_pc_open(const ripp_pc_srs* srs, const ripp_fr* coeffs, size_t rows, size_t cols, size_t stride, const ripp_g1j* y_coms, const ripp_fr* x, const ripp_fr* y,
+                     ripp_pc_opening* opening, ripp_fr* eval, ripp_stats* stats);
+/* BivariatePolynomialCommitment::verify (mod.rs:265-285) */
+int32_t ripp_pc_verify(const ripp_verifier_srs* v_srs, const ripp_gt* com, const ripp_fr* x, const ripp_fr* y, const ripp_fr* eval, const ripp_pc_opening* opening, size_t rounds, int32_t* accept);
+/* UnivariatePolynomialCommitment::commit / open / verify (mod.rs:340-388): the bivariate form of a flat coefficient array is that array with
+ * stride y_degree + 1 (mod.rs:316-338), the point is (z^(y_degree + 1), z) */
+int32_t ripp_pc_commit_univariate(const ripp_pc_srs* srs, const ripp_fr* coeffs, size_t len, ripp_gt* com, ripp_g1j* y_coms);
+int32_t ripp_pc_open_univariate(const ripp_pc_srs* srs, const ripp_fr* coeffs, size_t len, const ripp_g1j* y_coms, const ripp_fr* point,
+                                ripp_pc_opening* opening, ripp_fr* eval, ripp_stats* stats);
+int32_t ripp_pc_verify_univariate(const ripp_verifier_srs* v_srs, size_t max_degree, const ripp_gt* com, const ripp_fr* point, const ripp_fr* eval,
+                                  const ripp_pc_opening* opening, size_t rounds, int32_t* accept);
+
 /* ---- wire format: ark-serialize 0.4 images of the proof structs, host only ---------------------
  * compress = 0: `serialize_uncompressed`, 1: `serialize_compressed`.  Steps are passed in ROUND order and written reversed, as
  * GIPAProof stores them (gipa.rs:298-299).  Serialisers return the image size and write it when cap is large enough (out may be

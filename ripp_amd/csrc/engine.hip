@@ -39,6 +39,7 @@
 #include "fq_miller.hpp"
 #include "fq_scale.hpp"
 #include "fq_msm.hpp"
+#include "msm_batch.hpp"
 #include "vm_fold2.hpp"
 #include "host_fs.hpp"
 #include "wire.hpp"
@@ -251,6 +252,11 @@ struct Engine {
     DevBuf lines, partA, partB, jacG1, jacG2, tmpA, tmpB, tmpR, affG1, affG2;
     DevBuf qtab;                          // [u^j]Q table of the GLS G2 fold
     MsmScratch msm_scratch[2];
+    // batched shared-base MSM and the polynomial commitments (msm_batch.hpp, poly_commit_api.inc): the batch pipeline's scratch (sized for one chunk of rows),
+    // the uploaded scalar / coefficient matrix, the row results (projective and normalised), and the Fr vectors of an opening (partial evaluation, chunk sums, carries, quotient)
+    MsmScratch msm_batch; DevBuf pc_coef, pc_out, pc_yev, pc_h, pc_cin, pc_q, pc_aff;
+    uint32_t msm_batch_chunks = 0;        // chunks of rows the last batched MSM ran in (1: the whole batch in one pass)
+    void pc_release() { msm_batch.release(); for (DevBuf* b : {&pc_coef, &pc_out, &pc_yev, &pc_h, &pc_cin, &pc_q, &pc_aff}) b->release(); }
     DevBuf kzg_q[2];                      // quotient-polynomial coefficients of the (up to two concurrent) KZG openings
     PinBuf stage[4];                      // pinned staging of host-produced vectors: [0], [1] scalar vectors of the two concurrent MSMs, [2] r-powers, [3] gathered tails
     DevBuf kzg_bases[2];                  // sharded openings: this rank's residue class of the SRS powers, gathered contiguously
@@ -331,7 +337,7 @@ struct Engine {
         return aux;
     }
     // run-time switches: read from the environment ONCE per C-ABI call (get_engine), never inside round loops
-    struct Switches { bool no_vm = false, no_precompute = false, no_fold_tables = false, no_msm_glv = false, lp_one_lane = false, no_endo = false, no_fq = false, no_xscale = false, no_share = false, no_fuse = false, no_prebuild = false, fuse_tables = false, no_job_cache = false, no_lp_kara = false; } sw;
+    struct Switches { bool no_vm = false, no_precompute = false, no_fold_tables = false, no_msm_glv = false, lp_one_lane = false, no_endo = false, no_fq = false, no_xscale = false, no_share = false, no_fuse = false, no_prebuild = false, fuse_tables = false, no_job_cache = false, no_lp_kara = false, no_msm_batch = false; } sw;
     // crossover sizes: the member initialisers above are the defaults, the environment overrides them PER CALL (a test or
     // an A/B run flips them on a live engine)
     struct Sizes { size_t vm_lines_max, vm_fold_max, vm_tree_max, gls_split_max, msm_vm_merge_max, fold_tab_min, fq_min, lp_fq_min, vm_joint_max, vm_scale_max, tail_pipe_max, ml_fq_min, fq_min_g1, msm_lds_sort_min, msm_chunk_min; } defaults{};
@@ -381,6 +387,7 @@ struct Engine {
         { auto env_u32 = [](const char* k, uint32_t& v) { if (const char* s = std::getenv(k)) v = (uint32_t)std::strtoul(s, nullptr, 10); };
           env_u32("RIPP_COMM_TIMEOUT_MS", comm_timeout_ms); env_u32("RIPP_PLAN_DERATE_PCT", plan_derate_pct); env_u32("RIPP_N_DEVICES", n_devices_cfg);
           virtual_devices = false; if (const char* s = std::getenv("RIPP_VIRTUAL_DEVICES")) { n_devices_cfg = (uint32_t)std::strtoul(s, nullptr, 10); virtual_devices = true; } }
+        env_on("RIPP_NO_MSM_BATCH", sw.no_msm_batch);  // batched shared-base MSMs as a loop of single MSMs over the rows (A/B; the form the legacy MSM switches select too)
         env_on("RIPP_NO_PREBUILD", sw.no_prebuild);    // in-round G2 fold tables after the challenge (fold_g2_table), not in the host phase before it (job_prebuild_g2_tables)
         env_on("RIPP_NO_FUSE", sw.no_fuse);            // rounds 0 and 1 always fold one after the other (no three-quarter tables, no job_fold_fused)
         env_on("RIPP_NO_SHARE", sw.no_share);          // every pairing product walks its own G2 chain (no ChainSets grouping, no merged round 0 + look-ahead)
@@ -417,7 +424,7 @@ struct Engine {
         for (Engine* p : peers) { (void)hipSetDevice(p->device); p->destroy(); delete p; }
         if (!peers.empty()) { peers.clear(); (void)hipSetDevice(device); }
         for (DevBuf* b : {&lines, &partA, &partB, &jacG1, &jacG2, &tmpA, &tmpB, &tmpR, &affG1, &affG2, &qtab, &vm_flag, &scale_tab, &fold_tab1, &fold_mult, &fold_tab, &fold_jac1, &fold_jac2, &fix_flags, &scale_flags}) b->release();
-        msm_scratch[0].release(); msm_scratch[1].release(); kzg_q[0].release(); kzg_q[1].release(); kzg_bases[0].release(); kzg_bases[1].release(); job_cache.release();
+        msm_scratch[0].release(); msm_scratch[1].release(); kzg_q[0].release(); kzg_q[1].release(); kzg_bases[0].release(); kzg_bases[1].release(); job_cache.release(); pc_release();
         if (stream3) (void)hipStreamDestroy(stream3);
         if (stream4) (void)hipStreamDestroy(stream4); if (ev_join4) (void)hipEventDestroy(ev_join4);
         if (stream5) (void)hipStreamDestroy(stream5); if (ev_join5) (void)hipEventDestroy(ev_join5);
@@ -597,6 +604,85 @@ struct Engine {
         int32_t rc = msm_launch<F>(msm_scratch[0], stream, bases, scalars, n, bases_arrive); if (rc) return rc;
         if ((rc = sync())) return rc;
         *out_host = *reinterpret_cast<const Jac<F>*>(msm_scratch[0].host_out);
+        return RIPP_OK;
+    }
+
+    // ---- batched shared-base G1 MSM (msm_batch.hpp): out_dev[r] = sum_{i < cols} scalars[r * stride + i] * bases[i], r < rows -----------------------
+    // bases, scalars, out_dev: device memory.  ext (optional): the extended base array of EXACTLY the first `cols` bases (k_msm_extend_q with split 2), kept
+    // resident by a ripp_pc_srs; without it the array is built once per call -- never per row.  Enqueued on `stream`; the caller synchronises.
+    // Rows are processed in chunks when the scratch of the whole batch (digits and sorted indices grow with rows x windows x terms) does not fit
+    // ripp_config.mem_cap_bytes / free memory; every chunk runs the same plan, so a chunked run gives the same points.
+    // Legacy switches (no_msm_glv, no_fq, no_vm) and RIPP_NO_MSM_BATCH: the per-row loop of msm_launch, which honours them.
+    static size_t msm_batch_bytes(const MsmPlan& p, size_t R) {
+        const size_t W = R * (size_t)p.nwin, n = p.n, max_slots = n / p.ch + std::min<size_t>(p.nb, n) + 1, nseg = (p.nb + p.seg - 1) / p.seg;
+        return W * (n * 6 + (size_t)p.nb * 16 + 4 + max_slots * (sizeof(G1J) + 1) + ((size_t)p.nb + nseg + (nseg + MSM_SEG_FAN - 1) / MSM_SEG_FAN) * sizeof(G1J)) + 16;
+    }
+    int32_t msm_batch_dev(const G1A* bases, const QAff<Fp>* ext, const Fr* scalars, size_t rows, size_t cols, size_t stride, G1J* out_dev) {
+        msm_batch_chunks = 0;
+        if (rows == 0) return RIPP_OK;
+        hipStream_t st = stream; int32_t rc;
+        if (cols == 0) { const G1J inf = jac_inf<Fp>(); std::vector<G1J> z(rows, inf); HIPCHK(hipMemcpyAsync(out_dev, z.data(), rows * sizeof(G1J), hipMemcpyHostToDevice, st)); return sync(); }
+        if (sw.no_msm_batch || sw.no_msm_glv || sw.no_fq || sw.no_vm) {
+            for (size_t r = 0; r < rows; ++r) {
+                if ((rc = msm_launch<Fp>(msm_scratch[0], st, bases, scalars + r * stride, cols))) return rc;
+                HIPCHK(hipMemcpyAsync(out_dev + r, msm_scratch[0].out.p, sizeof(G1J), hipMemcpyDeviceToDevice, st));
+            }
+            return RIPP_OK;
+        }
+        MsmScratch& ms = msm_batch;
+        const MsmPlan p = msm_plan_batch(cols, 2, rows, msm_tune);
+        const size_t n = p.n, max_slots = n / p.ch + std::min<size_t>(p.nb, n) + 1;
+        // rows per chunk: grid.y and the 32-bit slot index of the fix-up kernels bound it first, then the memory budget (halving; one row always runs)
+        size_t R = std::min<size_t>(rows, std::min<size_t>(65535 / (size_t)p.nwin, (((size_t)1 << 32) - 1) / ((size_t)p.nwin * max_slots)));
+        R = std::max<size_t>(R, 1);
+        size_t held = 0; for (DevBuf* b : {&ms.digits, &ms.hist, &ms.offs, &ms.cursor, &ms.slotoffs, &ms.spw, &ms.sorted, &ms.slots, &ms.buckets, &ms.seg, &ms.seg2, &ms.flags}) held += b->cap;
+        while (R > 1 && !mem_fits(msm_batch_bytes(p, R), held)) R = (R + 1) / 2;
+        if (!ext) {
+            if ((rc = ms.ext.reserve(n * sizeof(G1A)))) return rc;
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_msm_extend_q<Fp>), dim3(nblk(cols, 256), 2), dim3(256), 0, st, bases, (uint32_t)cols, 2, ms.ext.as<QAff<Fp>>());
+            ext = ms.ext.as<QAff<Fp>>();
+        }
+        const size_t vm_lds = 4 * VM_EPW * VmCurve<Fp>::SLOTS * sizeof(VmSlot);
+        for (size_t r0 = 0; r0 < rows; r0 += R, ++msm_batch_chunks) {
+            const size_t Rc = std::min(R, rows - r0);
+            MsmPlan pb = p; pb.nwin = (int)(Rc * (size_t)p.nwin);                      // the chunk's virtual windows
+            const size_t W = (size_t)pb.nwin, nwb = W * p.nb;
+            uint32_t nseg = (p.nb + p.seg - 1) / p.seg;
+            if ((rc = ms.digits.reserve(W * n * sizeof(uint16_t))) || (rc = ms.hist.reserve(nwb * 4)) || (rc = ms.offs.reserve(nwb * 4)) ||
+                (rc = ms.cursor.reserve(nwb * 4)) || (rc = ms.slotoffs.reserve(nwb * 4)) || (rc = ms.spw.reserve(W * 4)) ||
+                (rc = ms.sorted.reserve(W * n * 4)) || (rc = ms.slots.reserve(W * max_slots * sizeof(G1J))) ||
+                (rc = ms.buckets.reserve(nwb * sizeof(G1J))) || (rc = ms.seg.reserve(W * nseg * sizeof(G1J))) ||
+                (rc = ms.seg2.reserve(W * ((nseg + MSM_SEG_FAN - 1) / MSM_SEG_FAN) * sizeof(G1J))) || (rc = ms.flags.reserve(W * max_slots + 16))) return rc;
+            HIPCHK(hipMemsetAsync(ms.hist.p, 0, nwb * 4, st));
+            const uint32_t tile = msm_sort_tile(pb);
+            hipLaunchKernelGGL(k_msm_digits_batch, dim3(nblk(cols, 256), (unsigned)Rc), dim3(256), 0, st, scalars + r0 * stride, (uint32_t)cols, stride, p, ms.digits.as<uint16_t>());
+            hipLaunchKernelGGL(k_msm_hist_lds, dim3(nblk(n, tile), pb.nwin), dim3(MSM_SORT_BLOCK), 0, st, ms.digits.as<uint16_t>(), pb, tile, ms.hist.as<uint32_t>());
+            hipLaunchKernelGGL(k_msm_scan, dim3(pb.nwin), dim3(1024), 0, st, ms.hist.as<uint32_t>(), pb, ms.offs.as<uint32_t>(), ms.cursor.as<uint32_t>(), ms.slotoffs.as<uint32_t>(), ms.spw.as<uint32_t>());
+            hipLaunchKernelGGL(k_msm_scatter_lds, dim3(nblk(n, tile), pb.nwin), dim3(MSM_SORT_BLOCK), 0, st, ms.digits.as<uint16_t>(), pb, tile, ms.cursor.as<uint32_t>(), ms.sorted.as<uint32_t>());
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_msm_slot_sum_q<Fp>), dim3(nblk(max_slots, 64), pb.nwin), dim3(64), 0, st, ext, pb, ms.hist.as<uint32_t>(), ms.offs.as<uint32_t>(),
+                               ms.slotoffs.as<uint32_t>(), ms.spw.as<uint32_t>(), ms.sorted.as<uint32_t>(), ms.slots.as<G1J>(), (uint32_t)max_slots, true, ms.flags.as<uint8_t>());
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_msm_slot_sum_fix_vm<Fp>), dim3(FIX_GRID), dim3(64), VM_EPW * VmCurve<Fp>::SLOTS * sizeof(VmSlot), st, bases, pb, ms.hist.as<uint32_t>(), ms.offs.as<uint32_t>(),
+                               ms.slotoffs.as<uint32_t>(), ms.spw.as<uint32_t>(), ms.sorted.as<uint32_t>(), ms.slots.as<G1J>(), (uint32_t)max_slots, ms.flags.as<uint8_t>(), (uint32_t*)nullptr);
+            uint32_t passes = 0;
+            for (uint32_t gs = 1; passes < (uint32_t)MSM_GROUP_PASSES && n / p.ch + 1 > (size_t)p.gmin * gs; gs *= MSM_SLOT_GROUP, ++passes)
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_msm_slot_group<Fp>), dim3(nblk(max_slots, 64), pb.nwin), dim3(64), 0, st, pb, ms.hist.as<uint32_t>(),
+                                   ms.slotoffs.as<uint32_t>(), ms.spw.as<uint32_t>(), ms.slots.as<G1J>(), (uint32_t)max_slots, gs, true);
+            if (nwb <= msm_vm_merge_max)
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_msm_vm_merge<Fp>), dim3(nblk(p.nb, 4 * VM_EPW), pb.nwin), dim3(256), vm_lds, st, pb, ms.hist.as<uint32_t>(), ms.slotoffs.as<uint32_t>(),
+                                   ms.slots.as<G1J>(), (uint32_t)max_slots, ms.buckets.as<G1J>(), passes);
+            else
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_msm_bucket_merge<Fp>), dim3(nblk(p.nb, 64), pb.nwin), dim3(64), 0, st, pb, ms.hist.as<uint32_t>(), ms.slotoffs.as<uint32_t>(),
+                                   ms.slots.as<G1J>(), (uint32_t)max_slots, ms.buckets.as<G1J>(), passes, true);
+            G1J* cur = ms.seg.as<G1J>(); G1J* nxt = ms.seg2.as<G1J>();
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_msm_vm_segments<Fp>), dim3(nblk(nseg, 4 * VM_EPW), pb.nwin), dim3(256), vm_lds, st, pb, ms.buckets.as<G1J>(), cur, nseg);
+            while (nseg > 1) {
+                const uint32_t nout = (nseg + MSM_SEG_FAN - 1) / MSM_SEG_FAN;
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_msm_vm_reduce<Fp>), dim3(nblk(nout, 4 * VM_EPW), pb.nwin), dim3(256), vm_lds, st, cur, nseg, nxt, nout);
+                std::swap(cur, nxt); nseg = nout;
+            }
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_msm_finish_vm_batch<Fp>), dim3(nblk(Rc, VM_EPW)), dim3(64), VM_EPW * VmCurve<Fp>::SLOTS * sizeof(VmSlot), st, p, (uint32_t)Rc, cur, out_dev + r0);
+            HIPCHK(hipGetLastError());
+        }
         return RIPP_OK;
     }
 
@@ -1514,7 +1600,7 @@ API int32_t ripp_release_scratch(void) {
     Engine* e = g_engine;
     if (hipSetDevice(e->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) { set_err("ripp_release_scratch: device synchronisation failed"); return RIPP_ERR_DEVICE; }
     for (DevBuf* b : {&e->lines, &e->partA, &e->partB, &e->jacG1, &e->jacG2, &e->tmpA, &e->tmpB, &e->tmpR, &e->affG1, &e->affG2, &e->qtab, &e->scale_tab, &e->fold_tab1, &e->fold_mult, &e->fold_tab, &e->fold_jac1, &e->fold_jac2, &e->fix_flags, &e->scale_flags}) b->release();
-    e->msm_scratch[0].release(); e->msm_scratch[1].release(); e->kzg_q[0].release(); e->kzg_q[1].release(); e->kzg_bases[0].release(); e->kzg_bases[1].release();
+    e->msm_scratch[0].release(); e->msm_scratch[1].release(); e->kzg_q[0].release(); e->kzg_q[1].release(); e->kzg_bases[0].release(); e->kzg_bases[1].release(); e->pc_release();
     for (PinBuf& pb : e->stage) pb.release();             // pinned host staging (up to 2 x 32 MB after a verifier call at n = 2^20)
     e->tab_owner = nullptr; e->g2tab_hi = nullptr; e->job_cache.release(); vec_caches_release();
     if (e->aux) { e->aux->destroy(); delete e->aux; e->aux = nullptr; }
@@ -2779,6 +2865,8 @@ API int32_t ripp_sipp_challenge(uint8_t seed[32], const ripp_gt* z_l, const ripp
 }
 
 #include "vec_api.inc"       // device-resident vectors (ripp_vec_*)
+
+#include "poly_commit_api.inc"      // KZG / bivariate / univariate polynomial commitments on a resident SRS handle, the batched shared-base MSM
 
 #include "wire_api.inc"      // CanonicalSerialize / CanonicalDeserialize images of the proof structs (zcash layout on BLS12-381, generic SWFlags layout on BLS12-377: wire.hpp)
 

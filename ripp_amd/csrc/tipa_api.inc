@@ -957,11 +957,20 @@ API int32_t ripp_tipa_tipp_verify(const ripp_verifier_srs* v_srs, const ripp_gt 
     return RIPP_OK;
 }
 
+static int32_t tipa_ssm_verify_core(Engine* e, const ripp_verifier_srs* v_srs, const ripp_gt* com_a, const ripp_g1j* com_t, const ripp_fr* scalar_b,
+                                    const ripp_gt* com_gt, const ripp_g1j* com_g1, size_t rounds, const ripp_g1j* base_a,
+                                    const ripp_g2j* final_ck_a, const ripp_g2j* opening_a, int32_t* accept);
 API int32_t ripp_tipa_ssm_verify(const ripp_verifier_srs* v_srs, const ripp_gt* com_a, const ripp_g1j* com_t, const ripp_fr* scalar_b,
                                  const ripp_gt* com_gt, const ripp_g1j* com_g1, size_t rounds, const ripp_g1j* base_a,
                                  const ripp_g2j* final_ck_a, const ripp_g2j* opening_a, int32_t* accept) {
     if (!v_srs || !com_a || !com_t || !scalar_b || !com_gt || !com_g1 || !base_a || !final_ck_a || !opening_a || !accept || rounds == 0) return RIPP_ERR_ARG;
     LOCK; ENGINE;
+    return tipa_ssm_verify_core(e, v_srs, com_a, com_t, scalar_b, com_gt, com_g1, rounds, base_a, final_ck_a, opening_a, accept);
+}
+// the verifier itself, engine in hand and the lock held by the caller (ripp_pc_verify runs it beside its KZG check)
+static int32_t tipa_ssm_verify_core(Engine* e, const ripp_verifier_srs* v_srs, const ripp_gt* com_a, const ripp_g1j* com_t, const ripp_fr* scalar_b,
+                                    const ripp_gt* com_gt, const ripp_g1j* com_g1, size_t rounds, const ripp_g1j* base_a,
+                                    const ripp_g2j* final_ck_a, const ripp_g2j* opening_a, int32_t* accept) {
     const VSrs v = load_vsrs(v_srs);
     Fp12 ca = load_gt(com_a); G1J ct = load_jac<Fp>(com_t);
     std::vector<Fr> trf(rounds);

@@ -18,6 +18,7 @@ use core::ffi::c_void;
 #[repr(C)] pub struct RippVec { _private: [u8; 0] }
 #[repr(C)] pub struct RippSippJob { _private: [u8; 0] }
 #[repr(C)] pub struct RippSrs { _private: [u8; 0] }
+#[repr(C)] pub struct RippPcSrs { _private: [u8; 0] }
 /// `ripp_allgather_fn`: host-supplied all-gather of the "callback" transport (recv holds `world` blocks of `bytes` in rank order; 0 = ok)
 pub type RippAllgatherFn = Option<unsafe extern "C" fn(user: *mut c_void, send: *const c_void, recv: *mut c_void, bytes: usize) -> i32>;
 /// `ripp_aggregate_proof` (AggregateProof, groth16_aggregation.rs:59-69): step arrays are caller-allocated, filled in ROUND order
@@ -38,6 +39,17 @@ pub struct RippAggregateProof {
     pub c_base_a: RippG1J, pub c_base_b: RippFr,
     pub c_final_ck_a: RippG2J, pub c_opening_a: RippG2J,
     pub c_kzg_c: RippFr,
+}
+/// `ripp_pc_opening` (OpeningProof, applications/poly_commit/mod.rs:142-146): step arrays are caller-allocated for log2(x_degree + 1) rounds, filled in ROUND order
+#[repr(C)] #[derive(Copy, Clone)]
+pub struct RippPcOpening {
+    pub com_gt: *mut RippGt,
+    pub com_g1: *mut RippG1J,
+    pub transcript: *mut RippFr,
+    pub base_a: RippG1J, pub base_b: RippFr,
+    pub final_ck_a: RippG2J, pub opening_a: RippG2J,
+    pub kzg_challenge: RippFr,
+    pub y_eval_comm: RippG1J, pub kzg_proof: RippG1J,
 }
 /// `ripp_verifier_srs` (VerifierSRS, tipa/mod.rs:104-110)
 #[repr(C)] #[derive(Copy, Clone, Default)]
@@ -184,6 +196,24 @@ extern "C" {
     pub fn ripp_tipa_tipp_verify(v_srs: *const RippVerifierSrs, com: *const RippGt, com_steps: *const RippGt, rounds: usize, base_a: *const RippG1J, base_b: *const RippG2J, final_ck_a: *const RippG2J, final_ck_b: *const RippG1J, opening_a: *const RippG2J, opening_b: *const RippG1J, r_shift: *const RippFr, accept: *mut i32) -> i32;
     pub fn ripp_tipa_ssm_verify(v_srs: *const RippVerifierSrs, com_a: *const RippGt, com_t: *const RippG1J, scalar_b: *const RippFr, com_gt: *const RippGt, com_g1: *const RippG1J, rounds: usize, base_a: *const RippG1J, final_ck_a: *const RippG2J, opening_a: *const RippG2J, accept: *mut i32) -> i32;
     pub fn ripp_verify_aggregate_proof(v_srs: *const RippVerifierSrs, vk: *const RippGroth16Vk, public_inputs: *const RippFr, n: usize, m: usize, proof: *const RippAggregateProof, accept: *mut i32) -> i32;
+    pub fn ripp_pc_univariate_degrees(degree: usize, x_degree: *mut usize, y_degree: *mut usize) -> i32;
+    pub fn ripp_pc_srs_setup(alpha: *const RippFr, beta: *const RippFr, x_degree: usize, y_degree: usize, srs: *mut *mut RippPcSrs) -> i32;
+    pub fn ripp_pc_srs_create(kzg_powers: *const RippG1A, y_degree: usize, h_beta_powers: *const RippG2J, x_degree: usize, g_beta: *const RippG1J, h_alpha: *const RippG2J, srs: *mut *mut RippPcSrs) -> i32;
+    pub fn ripp_pc_srs_destroy(srs: *mut RippPcSrs);
+    pub fn ripp_pc_srs_degrees(srs: *const RippPcSrs, x_degree: *mut usize, y_degree: *mut usize) -> i32;
+    pub fn ripp_pc_srs_verifier_key(srs: *const RippPcSrs, out: *mut RippVerifierSrs) -> i32;
+    pub fn ripp_pc_srs_kzg_powers(srs: *const RippPcSrs, out: *mut RippG1A) -> i32;
+    pub fn ripp_msm_g1_batch_a(bases: *const RippG1A, n: usize, scalars: *const RippFr, rows: usize, cols: usize, stride: usize, out: *mut RippG1J) -> i32;
+    pub fn ripp_msm_batch_chunks() -> i32;
+    pub fn ripp_kzg_commit(srs: *const RippPcSrs, coeffs: *const RippFr, len: usize, com: *mut RippG1J) -> i32;
+    pub fn ripp_kzg_open(srs: *const RippPcSrs, coeffs: *const RippFr, len: usize, point: *const RippFr, proof: *mut RippG1J, eval: *mut RippFr) -> i32;
+    pub fn ripp_kzg_verify(v_srs: *const RippVerifierSrs, com: *const RippG1J, point: *const RippFr, eval: *const RippFr, proof: *const RippG1J, accept: *mut i32) -> i32;
+    pub fn ripp_pc_commit(srs: *const RippPcSrs, coeffs: *const RippFr, rows: usize, cols: usize, stride: usize, com: *mut RippGt, y_coms: *mut RippG1J) -> i32;
+    pub fn ripp_pc_open(srs: *const RippPcSrs, coeffs: *const RippFr, rows: usize, cols: usize, stride: usize, y_coms: *const RippG1J, x: *const RippFr, y: *const RippFr, opening: *mut RippPcOpening, eval: *mut RippFr, stats: *mut RippStats) -> i32;
+    pub fn ripp_pc_verify(v_srs: *const RippVerifierSrs, com: *const RippGt, x: *const RippFr, y: *const RippFr, eval: *const RippFr, opening: *const RippPcOpening, rounds: usize, accept: *mut i32) -> i32;
+    pub fn ripp_pc_commit_univariate(srs: *const RippPcSrs, coeffs: *const RippFr, len: usize, com: *mut RippGt, y_coms: *mut RippG1J) -> i32;
+    pub fn ripp_pc_open_univariate(srs: *const RippPcSrs, coeffs: *const RippFr, len: usize, y_coms: *const RippG1J, point: *const RippFr, opening: *mut RippPcOpening, eval: *mut RippFr, stats: *mut RippStats) -> i32;
+    pub fn ripp_pc_verify_univariate(v_srs: *const RippVerifierSrs, max_degree: usize, com: *const RippGt, point: *const RippFr, eval: *const RippFr, opening: *const RippPcOpening, rounds: usize, accept: *mut i32) -> i32;
     pub fn ripp_ser_tipa_tipp_proof(com_steps: *const RippGt, rounds: usize, base_a: *const RippG1J, base_b: *const RippG2J, final_ck_a: *const RippG2J, final_ck_b: *const RippG1J, opening_a: *const RippG2J, opening_b: *const RippG1J, compress: i32, out: *mut u8, cap: usize) -> usize;
     pub fn ripp_de_tipa_tipp_proof(in_: *const u8, len: usize, compress: i32, with_tipa: i32, max_rounds: usize, rounds: *mut usize, com_steps: *mut RippGt, base_a: *mut RippG1J, base_b: *mut RippG2J, final_ck_a: *mut RippG2J, final_ck_b: *mut RippG1J, opening_a: *mut RippG2J, opening_b: *mut RippG1J) -> i32;
     pub fn ripp_ser_tipa_ssm_proof(com_gt: *const RippGt, com_g1: *const RippG1J, rounds: usize, base_a: *const RippG1J, base_b: *const RippFr, final_ck_a: *const RippG2J, opening_a: *const RippG2J, compress: i32, out: *mut u8, cap: usize) -> usize;
