@@ -444,6 +444,78 @@ int32_t ripp_pc_open_univariate(const ripp_pc_srs* srs, const ripp_fr* coeffs, s
 int32_t ripp_pc_verify_univariate(const ripp_verifier_srs* v_srs, size_t max_degree, const ripp_gt* com, const ripp_fr* point, const ripp_fr* eval,
                                   const ripp_pc_opening* opening, size_t rounds, int32_t* accept);
 
+/* ---- transparent polynomial commitments -- ip_proofs/src/applications/poly_commit/transparent.rs -----------------------------------
+ * BivariatePolynomialCommitment (:86-212: Pedersen commitments of the y-polynomials, committed to with AFGHO) and UnivariatePolynomialCommitment
+ * (:214-330), opened with two GIPAWithSSM arguments (tipa/structured_scalar_message.rs:56-128): the second tier over (y_polynomial_comms, powers
+ * of x) in GIPAWithSSM<MultiexponentiationInnerProduct<G1>, AFGHOCommitmentG1, IdentityCommitment<G1>>, the first tier over (y_eval_coeffs,
+ * powers of y) in GIPAWithSSM<ScalarInnerProduct, PedersenCommitment<G1>, IdentityCommitment<Fr>>.  Coefficient conventions as for ripp_pc_*.
+ * The reference's OpeningProof of this scheme is not CanonicalSerialize, so there is no wire format.  Single device. */
+/* UnivariatePolynomialCommitment::bivariate_degrees (transparent.rs:221-227): skew factor 4 from sqrt >= 8, else sqrt / 2; host only, needs no
+ * device.  degree >= 1 (RIPP_ERR_ARG for 0: the reference divides by a zero skew factor). */
+int32_t ripp_tpc_univariate_degrees(size_t degree, size_t* x_degree, size_t* y_degree);
+/* Resident commitment key: first_tier_ck (y_degree + 1 G1 points, affine, with the extended form the batched MSM gathers from) and second_tier_ck
+ * (x_degree + 1 G2 points).  Both x_degree + 1 and y_degree + 1 must be powers of two >= 2 (RIPP_ERR_POW2 otherwise): NARROWER than the
+ * reference, which accepts a tier of length 1 with zero rounds. */
+typedef struct ripp_tpc_ck ripp_tpc_ck;
+/* BivariatePolynomialCommitment::setup (transparent.rs:89-99) with the generators' seeds GIVEN instead of drawn: key i = (seed + i) * generator, the
+ * points of ripp_synth_g1(seed_g1, 0, 1, y_degree + 1) / ripp_synth_g2(seed_g2, 0, 1, x_degree + 1), generated on the device (tests and
+ * benchmarks; a deployment hashes to the curve and uses ripp_tpc_ck_create) */
+int32_t ripp_tpc_ck_setup(uint64_t seed_g1, uint64_t seed_g2, size_t x_degree, size_t y_degree, ripp_tpc_ck** ck);
+/* the same from caller-supplied keys: first_tier_ck[y_degree + 1], second_tier_ck[x_degree + 1] */
+int32_t ripp_tpc_ck_create(const ripp_g1a* first_tier_ck, size_t y_degree, const ripp_g2a* second_tier_ck, size_t x_degree, ripp_tpc_ck** ck);
+void    ripp_tpc_ck_destroy(ripp_tpc_ck* ck);
+int32_t ripp_tpc_ck_degrees(const ripp_tpc_ck* ck, size_t* x_degree, size_t* y_degree);       /* parse_bivariate_degrees_from_ck, transparent.rs:229-233 */
+int32_t ripp_tpc_ck_keys(const ripp_tpc_ck* ck, ripp_g1a* first_tier_ck /* [y_degree + 1] */, ripp_g2a* second_tier_ck /* [x_degree + 1] */);
+/* OpeningProof (transparent.rs:80-84): the step arrays are caller-allocated for r2 = log2(x_degree + 1) and r1 = log2(y_degree + 1) rounds and filled
+ * in ROUND order (GIPAProof stores them reversed, gipa.rs:298-299); projective members are any representative of the group element. */
+typedef struct {
+    ripp_gt* s_com_gt;                          /* second tier [r2][2]: com_1.0, com_2.0 (AFGHO) */
+    ripp_g1j* s_com_g1;                         /* [r2][2]: com_1.2[0], com_2.2[0] (the inner products) */
+    ripp_fr* s_transcript;                      /* [r2] */
+    ripp_g1j s_base_a; ripp_fr s_base_b;        /* r_base */
+    ripp_g1j y_eval_comm;
+    ripp_g1j* f_com_g1;                         /* first tier [r1][2]: com_1.0, com_2.0 (Pedersen) */
+    ripp_fr* f_com_fr;                          /* [r1][2]: com_1.2[0], com_2.2[0] (the inner products) */
+    ripp_fr* f_transcript;                      /* [r1] */
+    ripp_fr f_base_a, f_base_b;                 /* r_base */
+} ripp_tpc_opening;
+/* BivariatePolynomialCommitment::commit (transparent.rs:101-127): rows <= x_degree + 1 (missing rows are zero polynomials), cols <= y_degree + 1,
+ * stride >= cols.  One batched MSM over the resident first-tier keys gives y_coms[x_degree + 1]; com is their AFGHO commitment under second_tier_ck. */
+int32_t ripp_tpc_commit(const ripp_tpc_ck* ck, const ripp_fr* coeffs, size_t rows, size_t cols, size_t stride, ripp_gt* com, ripp_g1j* y_coms);
+/* BivariatePolynomialCommitment::open (transparent.rs:129-186) at (x, y); eval (optional) = p(x, y).  y_eval_coeffs stay on the device from the partial
+ * evaluation to the last first-tier fold. */
+int32_t ripp_tpc_open(const ripp_tpc_ck* ck, const ripp_fr* coeffs, size_t rows, size_t cols, size_t stride, const ripp_g1j* y_coms, const ripp_fr* x, const ripp_fr* y,
+                      ripp_tpc_opening* opening, ripp_fr* eval, ripp_stats* stats);
+/* BivariatePolynomialCommitment::verify (transparent.rs:188-212): the transparent verifier needs all keys, hence the resident handle; its two final-key
+ * MSMs run on the device against them */
+int32_t ripp_tpc_verify(const ripp_tpc_ck* ck, const ripp_gt* com, const ripp_fr* x, const ripp_fr* y, const ripp_fr* eval, const ripp_tpc_opening* opening, int32_t* accept);
+/* UnivariatePolynomialCommitment::commit / open / verify (transparent.rs:235-330): a flat coefficient array (stride y_degree + 1), the point (z^(y_degree + 1), z) */
+int32_t ripp_tpc_commit_univariate(const ripp_tpc_ck* ck, const ripp_fr* coeffs, size_t len, ripp_gt* com, ripp_g1j* y_coms);
+int32_t ripp_tpc_open_univariate(const ripp_tpc_ck* ck, const ripp_fr* coeffs, size_t len, const ripp_g1j* y_coms, const ripp_fr* point,
+                                 ripp_tpc_opening* opening, ripp_fr* eval, ripp_stats* stats);
+int32_t ripp_tpc_verify_univariate(const ripp_tpc_ck* ck, const ripp_gt* com, const ripp_fr* point, const ripp_fr* eval, const ripp_tpc_opening* opening, int32_t* accept);
+/* The two tier arguments on their own, from host slices; n a power of two >= 2 (RIPP_ERR_POW2), outputs as the members of ripp_tpc_opening.
+ * First tier: GIPAWithSSM<ScalarInnerProduct, PedersenCommitment<G1>, IdentityCommitment<Fr>>::prove_with_structured_scalar_message
+ * (structured_scalar_message.rs:66-84 over gipa.rs:181-312): message m and structured scalars b in Fr, keys ck in G1. */
+/* ripp_stats of the first tier (here and in ripp_tpc_open): fold_ms, host_ms and total_ms as elsewhere; miller_products_ms counts pairing products only, so the
+ * first tier adds nothing to it -- its commitments and inner products are total_ms less the other two. */
+int32_t ripp_gipa_ssm_scalar_prove(const ripp_fr* m, const ripp_fr* b, const ripp_g1a* ck, size_t n, ripp_g1j* com_g1 /* [r][2] */, ripp_fr* com_fr /* [r][2] */,
+                                   ripp_fr* transcript /* [r] */, ripp_fr* base_a, ripp_fr* base_b, ripp_stats* stats);
+/* ... ::verify_with_structured_scalar_message (structured_scalar_message.rs:86-127) in full: transcript replay, final key (one MSM), gipa_valid with the
+ * proof's own r_base.1 and base_valid with b_base recomputed from scalar_b.  com = (com_a: Pedersen commitment of m, com_t: <m, b>). */
+int32_t ripp_gipa_ssm_scalar_verify(const ripp_g1a* ck, size_t n, const ripp_g1j* com_a, const ripp_fr* com_t, const ripp_fr* scalar_b,
+                                    const ripp_g1j* com_g1, const ripp_fr* com_fr, const ripp_fr* base_a, const ripp_fr* base_b, int32_t* accept);
+/* Second tier: GIPAWithSSM<MultiexponentiationInnerProduct<G1>, AFGHOCommitmentG1, IdentityCommitment<G1>> (the rounds of ripp_tipa_ssm_prove without its KZG
+ * opening): message m in G1, b in Fr, keys ck in G2.  com = (com_a in GT: AFGHO commitment of m, com_t in G1: <m, b>). */
+int32_t ripp_gipa_ssm_mexp_prove(const ripp_g1j* m, const ripp_fr* b, const ripp_g2a* ck, size_t n, ripp_gt* com_gt /* [r][2] */, ripp_g1j* com_g1 /* [r][2] */,
+                                 ripp_fr* transcript /* [r] */, ripp_g1j* base_a, ripp_fr* base_b, ripp_stats* stats);
+int32_t ripp_gipa_ssm_mexp_verify(const ripp_g2a* ck, size_t n, const ripp_gt* com_a, const ripp_g1j* com_t, const ripp_fr* scalar_b,
+                                  const ripp_gt* com_gt, const ripp_g1j* com_g1, const ripp_g1j* base_a, const ripp_fr* base_b, int32_t* accept);
+/* UNSTABLE diagnostics, not part of the drop-in boundary (it serves tools/tpc_first_tier_ab.py and may change or go): the milliseconds the commitments and inner products of every round (key lengths n, n / 2, .. 2) of the LAST first-tier prover of this process
+ * took to reach the host; returns the number of rounds.  RIPP_TPC_CROSS_MIN (environment) moves the key length from which a round's two Pedersen
+ * commitments run as one crossed pass of the batched MSM pipeline instead of two single MSMs; unmeasured so far, hence off by default. */
+int32_t ripp_tpc_round_ms(double* out, size_t cap);
+
 /* ---- wire format: ark-serialize 0.4 images of the proof structs, host only ---------------------
  * compress = 0: `serialize_uncompressed`, 1: `serialize_compressed`.  Steps are passed in ROUND order and written reversed, as
  * GIPAProof stores them (gipa.rs:298-299).  Serialisers return the image size and write it when cap is large enough (out may be

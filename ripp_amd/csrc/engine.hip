@@ -40,6 +40,7 @@
 #include "fq_scale.hpp"
 #include "fq_msm.hpp"
 #include "msm_batch.hpp"
+#include "tpc.hpp"
 #include "vm_fold2.hpp"
 #include "host_fs.hpp"
 #include "wire.hpp"
@@ -255,8 +256,9 @@ struct Engine {
     // batched shared-base MSM and the polynomial commitments (msm_batch.hpp, poly_commit_api.inc): the batch pipeline's scratch (sized for one chunk of rows),
     // the uploaded scalar / coefficient matrix, the row results (projective and normalised), and the Fr vectors of an opening (partial evaluation, chunk sums, carries, quotient)
     MsmScratch msm_batch; DevBuf pc_coef, pc_out, pc_yev, pc_h, pc_cin, pc_q, pc_aff;
+    DevBuf tpc_m, tpc_m2, tpc_b, tpc_b2, tpc_k, tpc_k2, tpc_jac, tpc_part, tpc_out;      // first tier of the transparent commitment (tpc_api.inc): message, scalars, keys + partners, fold and result scratch
     uint32_t msm_batch_chunks = 0;        // chunks of rows the last batched MSM ran in (1: the whole batch in one pass)
-    void pc_release() { msm_batch.release(); for (DevBuf* b : {&pc_coef, &pc_out, &pc_yev, &pc_h, &pc_cin, &pc_q, &pc_aff}) b->release(); }
+    void pc_release() { msm_batch.release(); for (DevBuf* b : {&pc_coef, &pc_out, &pc_yev, &pc_h, &pc_cin, &pc_q, &pc_aff, &tpc_m, &tpc_m2, &tpc_b, &tpc_b2, &tpc_k, &tpc_k2, &tpc_jac, &tpc_part, &tpc_out}) b->release(); }
     DevBuf kzg_q[2];                      // quotient-polynomial coefficients of the (up to two concurrent) KZG openings
     PinBuf stage[4];                      // pinned staging of host-produced vectors: [0], [1] scalar vectors of the two concurrent MSMs, [2] r-powers, [3] gathered tails
     DevBuf kzg_bases[2];                  // sharded openings: this rank's residue class of the SRS powers, gathered contiguously
@@ -342,6 +344,12 @@ struct Engine {
     // an A/B run flips them on a live engine)
     struct Sizes { size_t vm_lines_max, vm_fold_max, vm_tree_max, gls_split_max, msm_vm_merge_max, fold_tab_min, fq_min, lp_fq_min, vm_joint_max, vm_scale_max, tail_pipe_max, ml_fq_min, fq_min_g1, msm_lds_sort_min, msm_chunk_min; } defaults{};
     MsmTune msm_tune;
+    // First-tier rounds of the transparent polynomial commitment (tpc_api.inc): key vectors of at least this length commit with the crossed two-row
+    // batch pass, shorter ones with two single MSMs on two streams.  UNMEASURED so far: whether and from which length the crossed form wins is what
+    // tools/tpc_first_tier_ab.py tabulates (its output belongs in profiles/tpc_first_tier_ab.txt, which does not exist yet), so no round takes the crossed
+    // form by default.  RIPP_TPC_CROSS_MIN overrides the bound per call (2: every round crossed).
+    static constexpr size_t TPC_CROSS_MIN = ~(size_t)0;
+    size_t tpc_cross_min = TPC_CROSS_MIN;
     // the hash-window look-ahead plan and a few whole-call choices (ripp_config: look_eighths, ranks_per_device, look_static, quiet_waits, agg_sequential, scale_no_fq)
     double cal_ms_per_pair = 0, cal_hash_bytes_per_ms = 0;        // look_plan's rates as measured by the last large proof of this process (0: not yet)
     int look_eighths = -1; double ranks_per_device = 1.0; bool look_static = false, quiet_waits_cfg = false, agg_sequential = false, scale_no_fq = false;
@@ -387,6 +395,7 @@ struct Engine {
         { auto env_u32 = [](const char* k, uint32_t& v) { if (const char* s = std::getenv(k)) v = (uint32_t)std::strtoul(s, nullptr, 10); };
           env_u32("RIPP_COMM_TIMEOUT_MS", comm_timeout_ms); env_u32("RIPP_PLAN_DERATE_PCT", plan_derate_pct); env_u32("RIPP_N_DEVICES", n_devices_cfg);
           virtual_devices = false; if (const char* s = std::getenv("RIPP_VIRTUAL_DEVICES")) { n_devices_cfg = (uint32_t)std::strtoul(s, nullptr, 10); virtual_devices = true; } }
+        tpc_cross_min = TPC_CROSS_MIN; env_sz("RIPP_TPC_CROSS_MIN", tpc_cross_min);      // crossed two-row commitments of the first-tier rounds from this key length on (A/B)
         env_on("RIPP_NO_MSM_BATCH", sw.no_msm_batch);  // batched shared-base MSMs as a loop of single MSMs over the rows (A/B; the form the legacy MSM switches select too)
         env_on("RIPP_NO_PREBUILD", sw.no_prebuild);    // in-round G2 fold tables after the challenge (fold_g2_table), not in the host phase before it (job_prebuild_g2_tables)
         env_on("RIPP_NO_FUSE", sw.no_fuse);            // rounds 0 and 1 always fold one after the other (no three-quarter tables, no job_fold_fused)
@@ -617,12 +626,16 @@ struct Engine {
         const size_t W = R * (size_t)p.nwin, n = p.n, max_slots = n / p.ch + std::min<size_t>(p.nb, n) + 1, nseg = (p.nb + p.seg - 1) / p.seg;
         return W * (n * 6 + (size_t)p.nb * 16 + 4 + max_slots * (sizeof(G1J) + 1) + ((size_t)p.nb + nseg + (nseg + MSM_SEG_FAN - 1) / MSM_SEG_FAN) * sizeof(G1J)) + 16;
     }
-    int32_t msm_batch_dev(const G1A* bases, const QAff<Fp>* ext, const Fr* scalars, size_t rows, size_t cols, size_t stride, G1J* out_dev) {
+    // cross_h != 0: the crossed form of tpc.hpp -- rows = 2, cols = 2 cross_h, scalars = ONE vector m of cols elements; row 0 = (m[h:], 0), row 1 = (0, m[:h]).
+    // The legacy switches have no crossed form: the caller asks msm_batch_legacy() first and runs two msm_launch calls instead.
+    bool msm_batch_legacy() const { return sw.no_msm_batch || sw.no_msm_glv || sw.no_fq || sw.no_vm; }
+    int32_t msm_batch_dev(const G1A* bases, const QAff<Fp>* ext, const Fr* scalars, size_t rows, size_t cols, size_t stride, G1J* out_dev, uint32_t cross_h = 0) {
         msm_batch_chunks = 0;
         if (rows == 0) return RIPP_OK;
         hipStream_t st = stream; int32_t rc;
+        if (cross_h && (rows != 2 || cols != 2 * (size_t)cross_h || msm_batch_legacy())) { set_err("msm_batch_dev: the crossed form takes two rows over 2 h bases on the batched pipeline"); return RIPP_ERR_ARG; }
         if (cols == 0) { const G1J inf = jac_inf<Fp>(); std::vector<G1J> z(rows, inf); HIPCHK(hipMemcpyAsync(out_dev, z.data(), rows * sizeof(G1J), hipMemcpyHostToDevice, st)); return sync(); }
-        if (sw.no_msm_batch || sw.no_msm_glv || sw.no_fq || sw.no_vm) {
+        if (msm_batch_legacy()) {
             for (size_t r = 0; r < rows; ++r) {
                 if ((rc = msm_launch<Fp>(msm_scratch[0], st, bases, scalars + r * stride, cols))) return rc;
                 HIPCHK(hipMemcpyAsync(out_dev + r, msm_scratch[0].out.p, sizeof(G1J), hipMemcpyDeviceToDevice, st));
@@ -655,6 +668,10 @@ struct Engine {
                 (rc = ms.seg2.reserve(W * ((nseg + MSM_SEG_FAN - 1) / MSM_SEG_FAN) * sizeof(G1J))) || (rc = ms.flags.reserve(W * max_slots + 16))) return rc;
             HIPCHK(hipMemsetAsync(ms.hist.p, 0, nwb * 4, st));
             const uint32_t tile = msm_sort_tile(pb);
+            if (cross_h) {
+                if (Rc != 2) { set_err("msm_batch_dev: the crossed form does not fit one chunk"); return RIPP_ERR_DEVICE; }
+                hipLaunchKernelGGL(k_tpc_digits_cross, dim3(nblk(cols, 256), 2), dim3(256), 0, st, scalars, cross_h, p, ms.digits.as<uint16_t>());
+            } else
             hipLaunchKernelGGL(k_msm_digits_batch, dim3(nblk(cols, 256), (unsigned)Rc), dim3(256), 0, st, scalars + r0 * stride, (uint32_t)cols, stride, p, ms.digits.as<uint16_t>());
             hipLaunchKernelGGL(k_msm_hist_lds, dim3(nblk(n, tile), pb.nwin), dim3(MSM_SORT_BLOCK), 0, st, ms.digits.as<uint16_t>(), pb, tile, ms.hist.as<uint32_t>());
             hipLaunchKernelGGL(k_msm_scan, dim3(pb.nwin), dim3(1024), 0, st, ms.hist.as<uint32_t>(), pb, ms.offs.as<uint32_t>(), ms.cursor.as<uint32_t>(), ms.slotoffs.as<uint32_t>(), ms.spw.as<uint32_t>());
@@ -2867,6 +2884,8 @@ API int32_t ripp_sipp_challenge(uint8_t seed[32], const ripp_gt* z_l, const ripp
 #include "vec_api.inc"       // device-resident vectors (ripp_vec_*)
 
 #include "poly_commit_api.inc"      // KZG / bivariate / univariate polynomial commitments on a resident SRS handle, the batched shared-base MSM
+
+#include "tpc_api.inc"       // transparent polynomial commitments on a resident key handle, the two GIPAWithSSM tier arguments
 
 #include "wire_api.inc"      // CanonicalSerialize / CanonicalDeserialize images of the proof structs (zcash layout on BLS12-381, generic SWFlags layout on BLS12-377: wire.hpp)
 

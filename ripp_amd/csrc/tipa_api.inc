@@ -19,7 +19,8 @@ struct VecBufCache { std::vector<DevBuf> bufs; bool full = false;
     void park(std::initializer_list<DevBuf*> l) { (void)hipDeviceSynchronize(); if (full) { for (DevBuf* b : l) b->release(); return; } bufs.resize(l.size()); size_t i = 0; for (DevBuf* b : l) { bufs[i].release(); std::swap(*b, bufs[i++]); } full = true; }
     void release() { for (DevBuf& b : bufs) b.release(); full = false; } };
 static VecBufCache g_tipp_cache, g_ssm_cache;
-static void vec_caches_release() { g_tipp_cache.release(); g_ssm_cache.release(); }
+static FoldPre g_tpc_pre;                  // second fold base of the first-tier key folds (tpc_api.inc)
+static void vec_caches_release() { g_tipp_cache.release(); g_ssm_cache.release(); g_tpc_pre.release(); }
 template <class F> static int32_t fold_precompute(Engine* e, hipStream_t st, const Affine<F>* hi, size_t half, FoldPre& fp) {
     fp.ready = false;
     if (half == 0 || half > e->vm_fold_max || e->sw.no_vm || e->sw.no_precompute) return RIPP_OK;
@@ -591,13 +592,13 @@ struct SsmVecs {
     }
 };
 
-// GIPA<MultiexponentiationInnerProduct<G1>, AFGHO-G1, SSMPlaceholder, Identity<G1>>::_prove (gipa.rs:181-312) + the KZG opening of
-// ck_a (ssm.rs:225-254).  Per round: two pairing products share one line launch, two G1 MSMs over the halves.
-static int32_t tipa_ssm_core(Engine* e, const ripp_srs* srs, SsmVecs& v, size_t n, ripp_gt* com_gt, ripp_g1j* com_g1, ripp_fr* transcript,
-                             G1A& ha, Fr& hs, G2A& hka, G2J* opening_a, Fr* kzg_c, ShardCtx sc = ShardCtx()) {
+// GIPA<MultiexponentiationInnerProduct<G1>, AFGHO-G1, SSMPlaceholder, Identity<G1>>::_prove (gipa.rs:181-312): the rounds alone, which are all of
+// GIPAWithSSM::prove_with_structured_scalar_message (ssm.rs:66-84; the second tier of the transparent polynomial commitment, tpc_api.inc).
+// Per round: two pairing products share one line launch, two G1 MSMs over the halves.  Steps and transcript in ROUND order; *rounds_out = their number.
+static int32_t tipa_ssm_rounds(Engine* e, SsmVecs& v, size_t n, ripp_gt* com_gt, ripp_g1j* com_g1, ripp_fr* transcript,
+                               G1A& ha, Fr& hs, G2A& hka, size_t* rounds_out, ShardCtx sc = ShardCtx()) {
     int32_t rc;
     size_t len = n, round = 0;                 // n = LOCAL length
-    const ShardCtx sc0 = sc;                   // the KZG opening is sharded by the ORIGINAL partition
     Fr prev_c = Fr::zero();
     std::vector<Fp12> rows(2 * N_LINES);
     for (;;) {
@@ -650,7 +651,14 @@ static int32_t tipa_ssm_core(Engine* e, const ripp_srs* srs, SsmVecs& v, size_t 
         len = split; ++round;
     }
     HIPCHK(hipMemcpy(&ha, v.A.p, sizeof ha, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(&hs, v.S.p, sizeof hs, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(&hka, v.KA.p, sizeof hka, hipMemcpyDeviceToHost));
-    const size_t rounds = round;
+    *rounds_out = round; return RIPP_OK;
+}
+// the rounds above + the KZG opening of ck_a (ssm.rs:225-254)
+static int32_t tipa_ssm_core(Engine* e, const ripp_srs* srs, SsmVecs& v, size_t n, ripp_gt* com_gt, ripp_g1j* com_g1, ripp_fr* transcript,
+                             G1A& ha, Fr& hs, G2A& hka, G2J* opening_a, Fr* kzg_c, ShardCtx sc = ShardCtx()) {
+    const ShardCtx sc0 = sc;                   // the KZG opening is sharded by the ORIGINAL partition
+    int32_t rc; size_t rounds = 0;
+    if ((rc = tipa_ssm_rounds(e, v, n, com_gt, com_g1, transcript, ha, hs, hka, &rounds, sc))) return rc;
     std::vector<Fr> tri(rounds);
     for (size_t i = 0; i < rounds; ++i) { Fr t; std::memcpy(&t, &transcript[rounds - 1 - i], sizeof t); tri[i] = inv(t); }         // ssm.rs:227-229
     Fr first; std::memcpy(&first, &transcript[rounds - 1], sizeof first);

@@ -19,6 +19,7 @@ use core::ffi::c_void;
 #[repr(C)] pub struct RippSippJob { _private: [u8; 0] }
 #[repr(C)] pub struct RippSrs { _private: [u8; 0] }
 #[repr(C)] pub struct RippPcSrs { _private: [u8; 0] }
+#[repr(C)] pub struct RippTpcCk { _private: [u8; 0] }
 /// `ripp_allgather_fn`: host-supplied all-gather of the "callback" transport (recv holds `world` blocks of `bytes` in rank order; 0 = ok)
 pub type RippAllgatherFn = Option<unsafe extern "C" fn(user: *mut c_void, send: *const c_void, recv: *mut c_void, bytes: usize) -> i32>;
 /// `ripp_aggregate_proof` (AggregateProof, groth16_aggregation.rs:59-69): step arrays are caller-allocated, filled in ROUND order
@@ -50,6 +51,20 @@ pub struct RippPcOpening {
     pub final_ck_a: RippG2J, pub opening_a: RippG2J,
     pub kzg_challenge: RippFr,
     pub y_eval_comm: RippG1J, pub kzg_proof: RippG1J,
+}
+/// `ripp_tpc_opening` (OpeningProof, applications/poly_commit/transparent.rs:80-84): step arrays are caller-allocated for log2(x_degree + 1) second-tier and
+/// log2(y_degree + 1) first-tier rounds, filled in ROUND order
+#[repr(C)] #[derive(Copy, Clone)]
+pub struct RippTpcOpening {
+    pub s_com_gt: *mut RippGt,
+    pub s_com_g1: *mut RippG1J,
+    pub s_transcript: *mut RippFr,
+    pub s_base_a: RippG1J, pub s_base_b: RippFr,
+    pub y_eval_comm: RippG1J,
+    pub f_com_g1: *mut RippG1J,
+    pub f_com_fr: *mut RippFr,
+    pub f_transcript: *mut RippFr,
+    pub f_base_a: RippFr, pub f_base_b: RippFr,
 }
 /// `ripp_verifier_srs` (VerifierSRS, tipa/mod.rs:104-110)
 #[repr(C)] #[derive(Copy, Clone, Default)]
@@ -214,6 +229,23 @@ extern "C" {
     pub fn ripp_pc_commit_univariate(srs: *const RippPcSrs, coeffs: *const RippFr, len: usize, com: *mut RippGt, y_coms: *mut RippG1J) -> i32;
     pub fn ripp_pc_open_univariate(srs: *const RippPcSrs, coeffs: *const RippFr, len: usize, y_coms: *const RippG1J, point: *const RippFr, opening: *mut RippPcOpening, eval: *mut RippFr, stats: *mut RippStats) -> i32;
     pub fn ripp_pc_verify_univariate(v_srs: *const RippVerifierSrs, max_degree: usize, com: *const RippGt, point: *const RippFr, eval: *const RippFr, opening: *const RippPcOpening, rounds: usize, accept: *mut i32) -> i32;
+    pub fn ripp_tpc_univariate_degrees(degree: usize, x_degree: *mut usize, y_degree: *mut usize) -> i32;
+    pub fn ripp_tpc_ck_setup(seed_g1: u64, seed_g2: u64, x_degree: usize, y_degree: usize, ck: *mut *mut RippTpcCk) -> i32;
+    pub fn ripp_tpc_ck_create(first_tier_ck: *const RippG1A, y_degree: usize, second_tier_ck: *const RippG2A, x_degree: usize, ck: *mut *mut RippTpcCk) -> i32;
+    pub fn ripp_tpc_ck_destroy(ck: *mut RippTpcCk);
+    pub fn ripp_tpc_ck_degrees(ck: *const RippTpcCk, x_degree: *mut usize, y_degree: *mut usize) -> i32;
+    pub fn ripp_tpc_ck_keys(ck: *const RippTpcCk, first_tier_ck: *mut RippG1A, second_tier_ck: *mut RippG2A) -> i32;
+    pub fn ripp_tpc_commit(ck: *const RippTpcCk, coeffs: *const RippFr, rows: usize, cols: usize, stride: usize, com: *mut RippGt, y_coms: *mut RippG1J) -> i32;
+    pub fn ripp_tpc_open(ck: *const RippTpcCk, coeffs: *const RippFr, rows: usize, cols: usize, stride: usize, y_coms: *const RippG1J, x: *const RippFr, y: *const RippFr, opening: *mut RippTpcOpening, eval: *mut RippFr, stats: *mut RippStats) -> i32;
+    pub fn ripp_tpc_verify(ck: *const RippTpcCk, com: *const RippGt, x: *const RippFr, y: *const RippFr, eval: *const RippFr, opening: *const RippTpcOpening, accept: *mut i32) -> i32;
+    pub fn ripp_tpc_commit_univariate(ck: *const RippTpcCk, coeffs: *const RippFr, len: usize, com: *mut RippGt, y_coms: *mut RippG1J) -> i32;
+    pub fn ripp_tpc_open_univariate(ck: *const RippTpcCk, coeffs: *const RippFr, len: usize, y_coms: *const RippG1J, point: *const RippFr, opening: *mut RippTpcOpening, eval: *mut RippFr, stats: *mut RippStats) -> i32;
+    pub fn ripp_tpc_verify_univariate(ck: *const RippTpcCk, com: *const RippGt, point: *const RippFr, eval: *const RippFr, opening: *const RippTpcOpening, accept: *mut i32) -> i32;
+    pub fn ripp_gipa_ssm_scalar_prove(m: *const RippFr, b: *const RippFr, ck: *const RippG1A, n: usize, com_g1: *mut RippG1J, com_fr: *mut RippFr, transcript: *mut RippFr, base_a: *mut RippFr, base_b: *mut RippFr, stats: *mut RippStats) -> i32;
+    pub fn ripp_gipa_ssm_scalar_verify(ck: *const RippG1A, n: usize, com_a: *const RippG1J, com_t: *const RippFr, scalar_b: *const RippFr, com_g1: *const RippG1J, com_fr: *const RippFr, base_a: *const RippFr, base_b: *const RippFr, accept: *mut i32) -> i32;
+    pub fn ripp_gipa_ssm_mexp_prove(m: *const RippG1J, b: *const RippFr, ck: *const RippG2A, n: usize, com_gt: *mut RippGt, com_g1: *mut RippG1J, transcript: *mut RippFr, base_a: *mut RippG1J, base_b: *mut RippFr, stats: *mut RippStats) -> i32;
+    pub fn ripp_gipa_ssm_mexp_verify(ck: *const RippG2A, n: usize, com_a: *const RippGt, com_t: *const RippG1J, scalar_b: *const RippFr, com_gt: *const RippGt, com_g1: *const RippG1J, base_a: *const RippG1J, base_b: *const RippFr, accept: *mut i32) -> i32;
+    pub fn ripp_tpc_round_ms(out: *mut f64, cap: usize) -> i32;
     pub fn ripp_ser_tipa_tipp_proof(com_steps: *const RippGt, rounds: usize, base_a: *const RippG1J, base_b: *const RippG2J, final_ck_a: *const RippG2J, final_ck_b: *const RippG1J, opening_a: *const RippG2J, opening_b: *const RippG1J, compress: i32, out: *mut u8, cap: usize) -> usize;
     pub fn ripp_de_tipa_tipp_proof(in_: *const u8, len: usize, compress: i32, with_tipa: i32, max_rounds: usize, rounds: *mut usize, com_steps: *mut RippGt, base_a: *mut RippG1J, base_b: *mut RippG2J, final_ck_a: *mut RippG2J, final_ck_b: *mut RippG1J, opening_a: *mut RippG2J, opening_b: *mut RippG1J) -> i32;
     pub fn ripp_ser_tipa_ssm_proof(com_gt: *const RippGt, com_g1: *const RippG1J, rounds: usize, base_a: *const RippG1J, base_b: *const RippFr, final_ck_a: *const RippG2J, opening_a: *const RippG2J, compress: i32, out: *mut u8, cap: usize) -> usize;

@@ -22,7 +22,7 @@ SCALARS = {"int32_t": "i32", "uint32_t": "u32", "size_t": "usize", "uint64_t": "
 STRUCTS = {"ripp_fp": "RippFp", "ripp_fr": "RippFr", "ripp_fp2": "RippFp2", "ripp_gt": "RippGt", "ripp_g1a": "RippG1A", "ripp_g1j": "RippG1J", "ripp_g2a": "RippG2A",
            "ripp_g2j": "RippG2J", "ripp_stats": "RippStats", "ripp_config": "RippConfig", "ripp_vec": "RippVec", "ripp_sipp_job": "RippSippJob", "ripp_srs": "RippSrs",
            "ripp_aggregate_proof": "RippAggregateProof", "ripp_verifier_srs": "RippVerifierSrs", "ripp_groth16_vk": "RippGroth16Vk",
-           "ripp_pc_srs": "RippPcSrs", "ripp_pc_opening": "RippPcOpening"}
+           "ripp_pc_srs": "RippPcSrs", "ripp_pc_opening": "RippPcOpening", "ripp_tpc_ck": "RippTpcCk", "ripp_tpc_opening": "RippTpcOpening"}
 
 
 def prototypes(text):

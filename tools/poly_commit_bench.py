@@ -9,7 +9,7 @@ The device rows call ripp_amd.poly_commit (libripp_hip.so); with --cpu-max the o
 is timed beside them up to that degree and every commitment / verdict is cross-checked.  Times include this module's host-side integer <->
 Montgomery conversions of the coefficients (a Rust host hands field elements over as they are).
 
---native adds the rows of the library's own entry points (ripp_kzg_* / ripp_pc_*: ripp_amd/poly_commit/native.py) with backend `mi355x-hip-native`, on the same
+--native adds the rows of the library's own entry points (ripp_kzg_* / ripp_pc_* / ripp_tpc_*: ripp_amd/poly_commit/native.py) with backend `mi355x-hip-native`, on the same
 polynomials and points, next to the rows above.  Those calls take Montgomery limbs, so their times hold no conversion -- what a Rust or C caller sees.  Every native
 commitment, proof and evaluation is cross-checked against the Python path's, and each verifier is run on the other side's proof."""
 import argparse, csv, os, random, sys, time
@@ -104,6 +104,26 @@ def main():
             t, (com, coms) = timed(lambda: T.commit(ck, p)); row(i, "transparent_ipa", "commit", degree, t)
             t, proof = timed(lambda: T.open(ck, p, coms, z)); row(i, "transparent_ipa", "open", degree, t)
             t, ok = timed(lambda: T.verify(ck, com, z, ev, proof)); assert ok; row(i, "transparent_ipa", "verify", degree, t)
+            if args.native:
+                if i == 1:
+                    NT = N.transparent.UnivariatePolynomialCommitment
+                    t, nck = timed(lambda: NT.setup(700, 900, degree)); row(1, "transparent_ipa", "setup", degree, t, NAT)
+                    k1, k2 = nck.keys(); assert np.array_equal(k1, ck[0][:, :12]) and np.array_equal(k2, ck[1][:, :24])
+                c, fz = P.frs(p), P.frs([z])[0]
+                t, (ncom, ncoms) = timed(lambda: NT.commit(nck, c)); row(i, "transparent_ipa", "commit", degree, t, NAT)
+                t, (nproof, nval) = timed(lambda: NT.open(nck, c, ncoms, fz)); row(i, "transparent_ipa", "open", degree, t, NAT)
+                t, ok = timed(lambda: NT.verify(nck, ncom, fz, nval, nproof)); assert ok; row(i, "transparent_ipa", "verify", degree, t, NAT)
+                assert np.array_equal(ncom, com) and same_g1(ncoms, coms) and fr_to_int(nval) == ev and same_g1(nproof["y_eval_comm"], proof["y_eval_comm"])
+                for tier, left_g1 in (("second_tier_ip_proof", False), ("first_tier_ip_proof", True)):       # member for member
+                    a, b = nproof[tier], proof[tier]; assert len(a["r_commitment_steps"]) == len(b["r_commitment_steps"])
+                    for sa, sb in zip(a["r_commitment_steps"], b["r_commitment_steps"]):
+                        for k in range(2):
+                            assert same_g1(sa[k][0], sb[k][0]) if left_g1 else np.array_equal(sa[k][0], sb[k][0])
+                            assert np.array_equal(sa[k][2][0], sb[k][2][0]) if left_g1 else same_g1(sa[k][2][0], sb[k][2][0])
+                    assert (np.array_equal(a["r_base"][0], b["r_base"][0]) if left_g1 else same_g1(a["r_base"][0], b["r_base"][0])) and np.array_equal(a["r_base"][1], b["r_base"][1])
+                assert T.verify(ck, ncom, z, ev, nproof) and NT.verify(nck, com, fz, nval, proof)         # each verifier on the other side's proof
+        if args.native:
+            nck.close()
 
 
 if __name__ == "__main__":
