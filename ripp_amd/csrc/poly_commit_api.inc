@@ -7,26 +7,64 @@
 // coefficient never meets host arithmetic and the quotient never visits the host.
 // Every entry point takes LOCK once and calls the unlocked cores; none calls an exported function.
 
+// UnivariatePolynomialCommitment::bivariate_degrees (mod.rs:299-306); host only, needs no device
+API int32_t ripp_pc_univariate_degrees(size_t degree, size_t* x_degree, size_t* y_degree) { return sqrt_split(degree, 16, "ripp_pc_univariate_degrees", "mod.rs:302-305", x_degree, y_degree); }
+
 extern "C++" {
-// the sqrt split with the reference's skew factor (mod.rs:299-306)
-static int32_t pc_univariate_degrees(size_t degree, size_t* x_degree, size_t* y_degree) {
-    if (degree >= ((size_t)1 << 62)) return RIPP_ERR_ARG;
-    const size_t v = degree + 1;
-    size_t lo = 0, hi = (size_t)1 << 31;                                                // floor(sqrt(v)) by bisection, then its ceiling
-    while (lo < hi) { const size_t mid = (lo + hi + 1) / 2; if (mid <= v / mid) lo = mid; else hi = mid - 1; }
-    const size_t s = lo * lo == v ? lo : lo + 1;
-    size_t sq = 1; while (sq < s) sq <<= 1;                                              // next_power_of_two
-    const size_t skew = sq >= 32 ? 16 : sq / 2;
-    if (skew == 0) { set_err("ripp_pc_univariate_degrees: degree 0 has no split (the reference divides by a zero skew factor, mod.rs:302-305)"); return RIPP_ERR_ARG; }
-    *x_degree = sq / skew - 1; *y_degree = sq * skew - 1;
+// ---- the two-tier core, shared with the transparent scheme (tpc_api.inc) ------------------------------------------------------------------------
+// A resident two-tier key as both schemes see it: ny first-tier G1 bases (KZG powers / Pedersen keys) with their extended GLV form for the batched MSM,
+// and the nx second-tier G2 keys of the AFGHO commitment.  pc_key / tpc_key build one from a handle.
+struct TwoTier { const G1A* bases; QAff<Fp>* ext; const G2A* ck; size_t nx, ny; };
+// the extended form once the bases are in place
+static int32_t two_tier_extend(Engine* e, const TwoTier& k) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_msm_extend_q<Fp>), dim3(nblk(k.ny, 256), 2), dim3(256), 0, e->stream, k.bases, (uint32_t)k.ny, 2, k.ext);
+    HIPCHK(hipGetLastError());
     return RIPP_OK;
 }
+// rows x cols coefficients resp. a flat array of len against the degrees of a key; noun: what the key is called in the error text
+static int32_t two_tier_fits(const char* who, const char* noun, const TwoTier& k, size_t rows, size_t cols) {
+    if (rows <= k.nx && cols <= k.ny) return RIPP_OK;
+    set_err(std::string(who) + ": " + std::to_string(rows) + " x " + std::to_string(cols) + " coefficients exceed " + noun + " (" + std::to_string(k.nx - 1) + ", " + std::to_string(k.ny - 1) + ")");
+    return RIPP_ERR_ARG;
 }
-// UnivariatePolynomialCommitment::bivariate_degrees (mod.rs:299-306); host only, needs no device
-API int32_t ripp_pc_univariate_degrees(size_t degree, size_t* x_degree, size_t* y_degree) {
-    if (!x_degree || !y_degree) return RIPP_ERR_ARG;
-    return pc_univariate_degrees(degree, x_degree, y_degree);
+static int32_t two_tier_flat_fits(const char* who, const char* noun, const TwoTier& k, size_t len) {
+    if (len <= k.nx * k.ny) return RIPP_OK;
+    set_err(std::string(who) + ": degree " + std::to_string(len - 1) + " exceeds " + noun + " " + std::to_string(k.nx * k.ny - 1)); return RIPP_ERR_ARG;
 }
+// commit (mod.rs:174-196, transparent.rs:101-127): the x_degree + 1 first-tier commitments of the rows (one batched MSM; missing rows are zero polynomials) in e->pc_out,
+// then their AFGHO commitment
+static int32_t two_tier_commit(Engine* e, const TwoTier& k, const Fr* dcoef, size_t rows, size_t cols, size_t stride, ripp_gt* com, ripp_g1j* y_coms) {
+    int32_t rc;
+    if ((rc = e->pc_out.reserve(k.nx * sizeof(G1J))) || (rc = e->pc_aff.reserve(k.nx * sizeof(G1A)))) return rc;
+    HIPCHK(hipMemsetAsync(e->pc_out.p, 0, k.nx * sizeof(G1J), e->stream));            // Z = 0: the identity
+    if ((rc = e->msm_batch_dev(k.bases, cols == k.ny ? k.ext : nullptr, dcoef, rows, cols, stride, e->pc_out.as<G1J>()))) return rc;
+    HIPCHK(hipMemcpyAsync(y_coms, e->pc_out.p, k.nx * sizeof(G1J), hipMemcpyDeviceToHost, e->stream));
+    if ((rc = e->normalize_dev<Fp>(e->pc_out.as<G1J>(), k.nx, e->pc_aff.as<G1A>()))) return rc;
+    if ((rc = e->sync())) return rc;
+    return pairing_product_dev(e, e->pc_aff.as<G1A>(), k.ck, k.nx, com);
+}
+// the head of open (mod.rs:198-240, transparent.rs:129-159) on a dense coefficient matrix in device memory: the statistics start over (*t_start), the powers of x go
+// into v.S (structured_scalar_power), y_eval_coeffs = the partial evaluation at x into e->pc_yev, *yc = y_eval_comm.  more(): what a scheme enqueues behind the powers of x.
+template <class More> static int32_t two_tier_open_prefix(Engine* e, const TwoTier& k, SsmVecs& v, const Fr* dcoef, size_t rows, size_t cols, size_t stride, const Fr& x,
+                                                          G1J* yc, double* t_start, More&& more) {
+    int32_t rc;
+    e->stats = ripp_stats{};
+    *t_start = now_ms();
+    const std::vector<Fr> xp = fr_powers(x, k.nx);
+    if ((rc = v.reserve(k.nx))) return rc;
+    HIPCHK(hipMemcpyAsync(v.S.p, xp.data(), k.nx * sizeof(Fr), hipMemcpyHostToDevice, e->stream));
+    if ((rc = more()) || (rc = e->pc_yev.reserve(k.ny * sizeof(Fr)))) return rc;
+    hipLaunchKernelGGL(k_pc_partial_eval, dim3(nblk(k.ny, 256)), dim3(256), 0, e->stream, dcoef, (uint32_t)rows, (uint32_t)cols, stride, v.S.as<Fr>(), (uint32_t)k.ny, e->pc_yev.as<Fr>());
+    HIPCHK(hipGetLastError());
+    return e->msm_dev<Fp>(k.bases, e->pc_yev.as<Fr>(), k.ny, yc);                      // synchronises: xp outlives its copy
+}
+// the second tier's vectors: y_polynomial_comms normalised into v.A, the key into v.KA (the powers of x are in v.S already)
+static int32_t two_tier_load_second(Engine* e, const TwoTier& k, SsmVecs& v, const ripp_g1j* y_coms) {
+    int32_t rc; if ((rc = ssm_load_message(e, v, y_coms, k.nx))) return rc;
+    HIPCHK(hipMemcpyAsync(v.KA.p, k.ck, k.nx * sizeof(G2A), hipMemcpyDeviceToDevice, e->stream));
+    return e->sync();
+}
+}  // extern "C++"
 
 // KZG powers g^{alpha^i}, i <= y_degree (affine, with their extended GLV form for the batched MSM), the second-tier SRS over h^{beta^i},
 // i <= 2 x_degree (the G1 side of that ripp_srs holds g only: SRS { g_alpha_powers: vec![g], .. }, mod.rs:165-170), its even powers as the
@@ -34,14 +72,14 @@ API int32_t ripp_pc_univariate_degrees(size_t degree, size_t* x_degree, size_t* 
 struct ripp_pc_srs { DevBuf powers, ext, ck; ripp_srs ip; size_t nx = 0, ny = 0; G1J g, g_beta; G2J h, h_alpha; };
 
 extern "C++" {
+static TwoTier pc_key(const ripp_pc_srs* s) { return {static_cast<const G1A*>(s->powers.p), static_cast<QAff<Fp>*>(s->ext.p), static_cast<const G2A*>(s->ck.p), s->nx, s->ny}; }
 static void pc_srs_free(ripp_pc_srs* s) { s->powers.release(); s->ext.release(); s->ck.release(); s->ip.gap.release(); s->ip.hbp.release(); delete s; }
 // the derived members once powers (ny G1A) and ip.hbp (2 nx - 1 G2A) are in place
 static int32_t pc_srs_finish(Engine* e, ripp_pc_srs* s) {
     int32_t rc; const size_t num = 2 * s->nx - 1;
     s->ip.num = num;
     if ((rc = s->ext.reserve(2 * s->ny * sizeof(G1A))) || (rc = s->ck.reserve(s->nx * sizeof(G2A))) || (rc = s->ip.gap.reserve(num * sizeof(G1A)))) return rc;
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_msm_extend_q<Fp>), dim3(nblk(s->ny, 256), 2), dim3(256), 0, e->stream, s->powers.as<G1A>(), (uint32_t)s->ny, 2, s->ext.as<QAff<Fp>>());
-    HIPCHK(hipGetLastError());
+    if ((rc = two_tier_extend(e, pc_key(s)))) return rc;
     if ((rc = gather_even<G2A>(e, s->ip.hbp.as<G2A>(), s->nx, s->ck.as<G2A>()))) return rc;
     const std::vector<G1A> gs(num, to_affine(s->g));
     HIPCHK(hipMemcpyAsync(s->ip.gap.p, gs.data(), num * sizeof(G1A), hipMemcpyHostToDevice, e->stream));
@@ -49,7 +87,7 @@ static int32_t pc_srs_finish(Engine* e, ripp_pc_srs* s) {
 }
 // structured_generators_scalar_power (tipa/mod.rs:372-391) into device memory, normalised: out[i] = s^i * g
 template <class F> static int32_t pc_powers_dev(Engine* e, const Affine<F>& g, const Fr& s, size_t num, Affine<F>* out) {
-    std::vector<Fr> pw(num); pw[0] = Fr::one(); for (size_t i = 1; i < num; ++i) pw[i] = mul(pw[i - 1], s);
+    const std::vector<Fr> pw = fr_powers(s, num);
     DevBuf& jac = std::is_same<F, Fp>::value ? e->jacG1 : e->jacG2; DevBuf& aff = std::is_same<F, Fp>::value ? e->affG1 : e->affG2;
     int32_t rc; Fr* dk;
     if ((rc = upload<Fr>(e, e->tmpR, pw.data(), num, &dk)) || (rc = jac.reserve(num * sizeof(Jac<F>))) || (rc = aff.reserve(sizeof(Affine<F>)))) return rc;
@@ -60,8 +98,7 @@ template <class F> static int32_t pc_powers_dev(Engine* e, const Affine<F>& g, c
     return e->sync();                                                                  // pw is the host source of an asynchronous copy
 }
 static bool pc_degrees_ok(size_t x_degree, size_t y_degree) {
-    const size_t nx = x_degree + 1;
-    return nx != 0 && !(nx & (nx - 1)) && x_degree < ((size_t)1 << 24) && y_degree < ((size_t)1 << 30);
+    return is_pow2(x_degree + 1) && x_degree < ((size_t)1 << 24) && y_degree < ((size_t)1 << 30);
 }
 }  // extern "C++"
 
@@ -141,8 +178,7 @@ static int32_t kzg_quotient_dev(Engine* e, const Fr* dp, size_t m, const Fr& z, 
     const size_t nchunk = (m + KZG_CHUNK - 1) / KZG_CHUNK, per = (nchunk + KZG_SCAN_LANES - 1) / KZG_SCAN_LANES;
     int32_t rc;
     if ((rc = e->pc_h.reserve(nchunk * sizeof(Fr))) || (rc = e->pc_cin.reserve(nchunk * sizeof(Fr))) || (rc = e->pc_q.reserve((m + 1) * sizeof(Fr)))) return rc;
-    auto pow_u = [](Fr b, size_t k) { Fr r = Fr::one(); while (k) { if (k & 1) r = mul(r, b); b = mul(b, b); k >>= 1; } return r; };
-    const Fr zT = pow_u(z, KZG_CHUNK), zTper = pow_u(zT, per);
+    const Fr zT = fr_pow_u(z, KZG_CHUNK), zTper = fr_pow_u(zT, per);
     Fr* const q = e->pc_q.as<Fr>();                                                    // q[0 .. m - 1), then one slot for p(z)
     hipLaunchKernelGGL(k_kzg_chunk_sums, dim3(nblk(nchunk, 256)), dim3(256), 0, e->stream, dp, (uint32_t)m, z, e->pc_h.as<Fr>());
     hipLaunchKernelGGL(k_kzg_carry_scan, dim3(1), dim3(KZG_SCAN_LANES), 0, e->stream, e->pc_h.as<Fr>(), (uint32_t)nchunk, (uint32_t)per, zT, zTper, e->pc_cin.as<Fr>());
@@ -152,28 +188,17 @@ static int32_t kzg_quotient_dev(Engine* e, const Fr* dp, size_t m, const Fr& z, 
     return e->sync();
 }
 // KZG::open (mod.rs:90-109) of a polynomial in device memory: proof = MSM(powers, quotient), eval = p(z)
-static int32_t kzg_open_dev(Engine* e, const ripp_pc_srs* s, const Fr* dp, size_t m, const Fr& z, G1J* proof, Fr* eval) {
+static int32_t kzg_open_dev(Engine* e, const G1A* powers, const Fr* dp, size_t m, const Fr& z, G1J* proof, Fr* eval) {
     int32_t rc = kzg_quotient_dev(e, dp, m, z, eval); if (rc) return rc;
     *proof = jac_inf<Fp>();
     if (m < 2) return RIPP_OK;                                                        // a constant: the quotient is the zero polynomial
-    return e->msm_dev<Fp>(const_cast<ripp_pc_srs*>(s)->powers.as<G1A>(), e->pc_q.as<Fr>(), m - 1, proof);
+    return e->msm_dev<Fp>(powers, e->pc_q.as<Fr>(), m - 1, proof);
 }
 // e(com - g * eval, h) == e(proof, h_alpha - h * point)   (KZG::verify, mod.rs:111-119)
 static int32_t kzg_verify_core(Engine* e, const VSrs& v, const G1J& com, const Fr& point, const Fr& eval, const G1J& proof, bool* ok) {
     const G1J l1 = add(com, neg(smul_host(to_affine(v.g), eval)));
     const G2J r2 = add(v.h_alpha, neg(smul_host(to_affine(v.h), point)));
     return pairing_eq(e, l1, v.h, proof, r2, ok);
-}
-// the x_degree + 1 KZG commitments of the rows (one batched MSM; missing rows are zero polynomials) in e->pc_out, then the AFGHO commitment (mod.rs:174-196)
-static int32_t pc_commit_dev(Engine* e, const ripp_pc_srs* s, const Fr* dcoef, size_t rows, size_t cols, size_t stride, ripp_gt* com, ripp_g1j* y_coms) {
-    ripp_pc_srs* sm = const_cast<ripp_pc_srs*>(s); int32_t rc;
-    if ((rc = e->pc_out.reserve(s->nx * sizeof(G1J))) || (rc = e->pc_aff.reserve(s->nx * sizeof(G1A)))) return rc;
-    HIPCHK(hipMemsetAsync(e->pc_out.p, 0, s->nx * sizeof(G1J), e->stream));            // Z = 0: the identity
-    if ((rc = e->msm_batch_dev(sm->powers.as<G1A>(), cols == s->ny ? sm->ext.as<QAff<Fp>>() : nullptr, dcoef, rows, cols, stride, e->pc_out.as<G1J>()))) return rc;
-    HIPCHK(hipMemcpyAsync(y_coms, e->pc_out.p, s->nx * sizeof(G1J), hipMemcpyDeviceToHost, e->stream));
-    if ((rc = e->normalize_dev<Fp>(e->pc_out.as<G1J>(), s->nx, e->pc_aff.as<G1A>()))) return rc;
-    if ((rc = e->sync())) return rc;
-    return pairing_product_dev(e, e->pc_aff.as<G1A>(), sm->ck.as<G2A>(), s->nx, com);
 }
 }  // extern "C++"
 
@@ -202,7 +227,7 @@ API int32_t ripp_kzg_commit(const ripp_pc_srs* s, const ripp_fr* coeffs, size_t 
     if (len > s->ny) { set_err("ripp_kzg_commit: " + std::to_string(len) + " coefficients, " + std::to_string(s->ny) + " powers (assert at mod.rs:82)"); return RIPP_ERR_ARG; }
     LOCK; ENGINE;
     G1J res = jac_inf<Fp>(); int32_t rc; Fr* dc;
-    if (len && ((rc = upload<Fr>(e, e->pc_coef, coeffs, len, &dc)) || (rc = e->msm_dev<Fp>(const_cast<ripp_pc_srs*>(s)->powers.as<G1A>(), dc, len, &res)))) return rc;
+    if (len && ((rc = upload<Fr>(e, e->pc_coef, coeffs, len, &dc)) || (rc = e->msm_dev<Fp>(pc_key(s).bases, dc, len, &res)))) return rc;
     std::memcpy(com, &res, sizeof res); return RIPP_OK;
 }
 // KZG::open (mod.rs:90-109); eval (optional) = p(point), the remainder the reference drops
@@ -212,7 +237,7 @@ API int32_t ripp_kzg_open(const ripp_pc_srs* s, const ripp_fr* coeffs, size_t le
     if (len > s->ny) { set_err("ripp_kzg_open: " + std::to_string(len) + " coefficients, " + std::to_string(s->ny) + " powers (assert at mod.rs:95)"); return RIPP_ERR_ARG; }
     LOCK; ENGINE;
     G1J pr; Fr ev; int32_t rc; Fr* dc;
-    if ((rc = upload<Fr>(e, e->pc_coef, coeffs, len, &dc)) || (rc = kzg_open_dev(e, s, dc, len, load_fr(point), &pr, &ev))) return rc;
+    if ((rc = upload<Fr>(e, e->pc_coef, coeffs, len, &dc)) || (rc = kzg_open_dev(e, pc_key(s).bases, dc, len, load_fr(point), &pr, &ev))) return rc;
     std::memcpy(proof, &pr, sizeof pr); if (eval) std::memcpy(eval, &ev, sizeof ev);
     return RIPP_OK;
 }
@@ -228,10 +253,10 @@ API int32_t ripp_kzg_verify(const ripp_verifier_srs* v_srs, const ripp_g1j* com,
 // polynomials), j < cols <= y_degree + 1.  com = the AFGHO commitment to the x_degree + 1 KZG commitments y_coms.
 API int32_t ripp_pc_commit(const ripp_pc_srs* s, const ripp_fr* coeffs, size_t rows, size_t cols, size_t stride, ripp_gt* com, ripp_g1j* y_coms) {
     if (!s || !com || !y_coms || (rows && cols && !coeffs) || stride < cols) return RIPP_ERR_ARG;
-    if (rows > s->nx || cols > s->ny) { set_err("ripp_pc_commit: " + std::to_string(rows) + " x " + std::to_string(cols) + " coefficients exceed the SRS degrees (" + std::to_string(s->nx - 1) + ", " + std::to_string(s->ny - 1) + ")"); return RIPP_ERR_ARG; }
+    int32_t rc; if ((rc = two_tier_fits("ripp_pc_commit", "the SRS degrees", pc_key(s), rows, cols))) return rc;
     LOCK; ENGINE;
-    Fr* dc; int32_t rc = pc_upload_matrix(e, coeffs, rows, cols, stride, &dc); if (rc) return rc;
-    return pc_commit_dev(e, s, dc, rows, cols, cols, com, y_coms);
+    Fr* dc; if ((rc = pc_upload_matrix(e, coeffs, rows, cols, stride, &dc))) return rc;
+    return two_tier_commit(e, pc_key(s), dc, rows, cols, cols, com, y_coms);
 }
 
 extern "C++" {
@@ -239,32 +264,19 @@ static bool pc_opening_ok(const ripp_pc_opening* o) { return o && o->com_gt && o
 // BivariatePolynomialCommitment::open (mod.rs:198-263) on a dense coefficient matrix in device memory
 static int32_t pc_open_dev(Engine* e, const ripp_pc_srs* s, const Fr* dcoef, size_t rows, size_t cols, size_t stride, const ripp_g1j* y_coms, const Fr& x, const Fr& y,
                            ripp_pc_opening* o, ripp_fr* eval, ripp_stats* st) {
-    ripp_pc_srs* sm = const_cast<ripp_pc_srs*>(s); int32_t rc;
-    const size_t nx = s->nx, ny = s->ny;
-    e->stats = ripp_stats{};
-    const double t_start = now_ms();
-    std::vector<Fr> xp(nx); xp[0] = Fr::one(); for (size_t i = 1; i < nx; ++i) xp[i] = mul(xp[i - 1], x);            // structured_scalar_power (mod.rs:210-214)
-    SsmVecs v; if ((rc = v.reserve(nx))) return rc;
-    HIPCHK(hipMemcpyAsync(v.S.p, xp.data(), nx * sizeof(Fr), hipMemcpyHostToDevice, e->stream));
-    if ((rc = e->pc_yev.reserve(ny * sizeof(Fr)))) return rc;
-    hipLaunchKernelGGL(k_pc_partial_eval, dim3(nblk(ny, 256)), dim3(256), 0, e->stream, dcoef, (uint32_t)rows, (uint32_t)cols, stride, v.S.as<Fr>(), (uint32_t)ny, e->pc_yev.as<Fr>());
-    HIPCHK(hipGetLastError());
-    G1J yc, kp; Fr ev;
-    if ((rc = e->msm_dev<Fp>(sm->powers.as<G1A>(), e->pc_yev.as<Fr>(), ny, &yc))) return rc;                           // y_eval_comm (mod.rs:236-240)
-    if ((rc = kzg_open_dev(e, s, e->pc_yev.as<Fr>(), ny, y, &kp, &ev))) return rc;                                     // kzg_proof (mod.rs:252-256), p(x, y)
+    const TwoTier k = pc_key(s); int32_t rc;
+    SsmVecs v; G1J yc, kp; Fr ev; double t_start;
+    if ((rc = two_tier_open_prefix(e, k, v, dcoef, rows, cols, stride, x, &yc, &t_start, []() { return RIPP_OK; }))) return rc;          // y_eval_comm (mod.rs:236-240)
+    if ((rc = kzg_open_dev(e, k.bases, e->pc_yev.as<Fr>(), k.ny, y, &kp, &ev))) return rc;                               // kzg_proof (mod.rs:252-256), p(x, y)
     // the second tier: TIPAWithSSM over (y_polynomial_comms, powers of x) under ck_1 (mod.rs:242-250)
-    HIPCHK(hipMemcpyAsync(v.jac1.p, y_coms, nx * sizeof(G1J), hipMemcpyHostToDevice, e->stream)); if ((rc = e->normalize_dev<Fp>(v.jac1.as<G1J>(), nx, v.A.as<G1A>()))) return rc;
-    HIPCHK(hipMemcpyAsync(v.KA.p, sm->ck.p, nx * sizeof(G2A), hipMemcpyDeviceToDevice, e->stream)); if ((rc = e->sync())) return rc;
+    if ((rc = two_tier_load_second(e, k, v, y_coms))) return rc;
     G1A ha; Fr hs; G2A hka; G2J oa; Fr c;
-    if ((rc = tipa_ssm_core(e, &s->ip, v, nx, o->com_gt, o->com_g1, o->transcript, ha, hs, hka, &oa, &c))) return rc;
+    if ((rc = tipa_ssm_core(e, &s->ip, v, k.nx, o->com_gt, o->com_g1, o->transcript, ha, hs, hka, &oa, &c))) return rc;
     const G1J ja = to_jac(ha); const G2J jka = to_jac(hka);
     std::memcpy(&o->base_a, &ja, sizeof ja); std::memcpy(&o->base_b, &hs, sizeof hs); std::memcpy(&o->final_ck_a, &jka, sizeof jka); std::memcpy(&o->opening_a, &oa, sizeof oa);
     std::memcpy(&o->kzg_challenge, &c, sizeof c); std::memcpy(&o->y_eval_comm, &yc, sizeof yc); std::memcpy(&o->kzg_proof, &kp, sizeof kp);
     if (eval) std::memcpy(eval, &ev, sizeof ev);
-    e->collect_kernel_stats();
-    e->stats.total_ms = now_ms() - t_start; e->stats.device_bytes = g_dev_bytes.load(std::memory_order_relaxed);
-    if (st) *st = e->stats;
-    return RIPP_OK;
+    return finish_stats(e, t_start, st);
 }
 static int32_t pc_verify_core(Engine* e, const ripp_verifier_srs* v_srs, const ripp_gt* com, const Fr& x, const Fr& y, const Fr& eval, const ripp_pc_opening* o, size_t rounds, int32_t* accept) {
     int32_t ip_ok = 0; bool kzg_ok = false; int32_t rc;
@@ -273,7 +285,6 @@ static int32_t pc_verify_core(Engine* e, const ripp_verifier_srs* v_srs, const r
     if ((rc = kzg_verify_core(e, load_vsrs(v_srs), load_jac<Fp>(&o->y_eval_comm), y, eval, load_jac<Fp>(&o->kzg_proof), &kzg_ok))) return rc;                          // mod.rs:279-282
     *accept = (ip_ok && kzg_ok) ? 1 : 0; return RIPP_OK;
 }
-static Fr fr_pow_u(Fr b, size_t k) { Fr r = Fr::one(); while (k) { if (k & 1) r = mul(r, b); b = mul(b, b); k >>= 1; } return r; }
 }  // extern "C++"
 
 // BivariatePolynomialCommitment::open (mod.rs:198-263).  opening: caller-allocated step arrays for rounds = log2(x_degree + 1), filled in ROUND order like
@@ -281,10 +292,10 @@ static Fr fr_pow_u(Fr b, size_t k) { Fr r = Fr::one(); while (k) { if (k & 1) r 
 API int32_t ripp_pc_open(const ripp_pc_srs* s, const ripp_fr* coeffs, size_t rows, size_t cols, size_t stride, const ripp_g1j* y_coms, const ripp_fr* x, const ripp_fr* y,
                          ripp_pc_opening* opening, ripp_fr* eval, ripp_stats* st) {
     if (!s || !y_coms || !x || !y || !pc_opening_ok(opening) || (rows && cols && !coeffs) || stride < cols) return RIPP_ERR_ARG;
-    if (rows > s->nx || cols > s->ny) { set_err("ripp_pc_open: " + std::to_string(rows) + " x " + std::to_string(cols) + " coefficients exceed the SRS degrees (" + std::to_string(s->nx - 1) + ", " + std::to_string(s->ny - 1) + ")"); return RIPP_ERR_ARG; }
+    int32_t rc; if ((rc = two_tier_fits("ripp_pc_open", "the SRS degrees", pc_key(s), rows, cols))) return rc;
     if (s->nx < 2) return RIPP_ERR_POW2;
     LOCK; ENGINE;
-    Fr* dc; int32_t rc = pc_upload_matrix(e, coeffs, rows, cols, stride, &dc); if (rc) return rc;
+    Fr* dc; if ((rc = pc_upload_matrix(e, coeffs, rows, cols, stride, &dc))) return rc;
     return pc_open_dev(e, s, dc, rows, cols, cols, y_coms, load_fr(x), load_fr(y), opening, eval, st);
 }
 // BivariatePolynomialCommitment::verify (mod.rs:265-285)
@@ -299,24 +310,24 @@ API int32_t ripp_pc_verify(const ripp_verifier_srs* v_srs, const ripp_gt* com, c
 API int32_t ripp_pc_commit_univariate(const ripp_pc_srs* s, const ripp_fr* coeffs, size_t len, ripp_gt* com, ripp_g1j* y_coms) {
     if (!s || !com || !y_coms || (len && !coeffs)) return RIPP_ERR_ARG;
     len = pc_stripped_len(coeffs, len);
-    if (len > s->nx * s->ny) { set_err("ripp_pc_commit_univariate: degree " + std::to_string(len - 1) + " exceeds the SRS's " + std::to_string(s->nx * s->ny - 1)); return RIPP_ERR_ARG; }
+    int32_t rc; if ((rc = two_tier_flat_fits("ripp_pc_commit_univariate", "the SRS's", pc_key(s), len))) return rc;
     LOCK; ENGINE;
-    Fr* dc; size_t rows; int32_t rc = pc_upload_flat(e, coeffs, len, s->ny, &rows, &dc); if (rc) return rc;
-    return pc_commit_dev(e, s, dc, rows, rows ? s->ny : 0, s->ny, com, y_coms);
+    Fr* dc; size_t rows; if ((rc = pc_upload_flat(e, coeffs, len, s->ny, &rows, &dc))) return rc;
+    return two_tier_commit(e, pc_key(s), dc, rows, rows ? s->ny : 0, s->ny, com, y_coms);
 }
 API int32_t ripp_pc_open_univariate(const ripp_pc_srs* s, const ripp_fr* coeffs, size_t len, const ripp_g1j* y_coms, const ripp_fr* point, ripp_pc_opening* opening, ripp_fr* eval, ripp_stats* st) {
     if (!s || !y_coms || !point || !pc_opening_ok(opening) || (len && !coeffs)) return RIPP_ERR_ARG;
     len = pc_stripped_len(coeffs, len);
-    if (len > s->nx * s->ny) { set_err("ripp_pc_open_univariate: degree " + std::to_string(len - 1) + " exceeds the SRS's " + std::to_string(s->nx * s->ny - 1)); return RIPP_ERR_ARG; }
+    int32_t rc; if ((rc = two_tier_flat_fits("ripp_pc_open_univariate", "the SRS's", pc_key(s), len))) return rc;
     if (s->nx < 2) return RIPP_ERR_POW2;
     LOCK; ENGINE;
-    Fr* dc; size_t rows; int32_t rc = pc_upload_flat(e, coeffs, len, s->ny, &rows, &dc); if (rc) return rc;
+    Fr* dc; size_t rows; if ((rc = pc_upload_flat(e, coeffs, len, s->ny, &rows, &dc))) return rc;
     const Fr z = load_fr(point);
     return pc_open_dev(e, s, dc, rows, rows ? s->ny : 0, s->ny, y_coms, fr_pow_u(z, s->ny), z, opening, eval, st);               // mod.rs:362-369
 }
 API int32_t ripp_pc_verify_univariate(const ripp_verifier_srs* v_srs, size_t max_degree, const ripp_gt* com, const ripp_fr* point, const ripp_fr* eval, const ripp_pc_opening* opening, size_t rounds, int32_t* accept) {
     if (!v_srs || !com || !point || !eval || !pc_opening_ok(opening) || !accept || rounds == 0) return RIPP_ERR_ARG;
-    size_t xd, yd; int32_t rc = pc_univariate_degrees(max_degree, &xd, &yd); if (rc) return rc;
+    size_t xd, yd; int32_t rc = sqrt_split(max_degree, 16, "ripp_pc_univariate_degrees", "mod.rs:302-305", &xd, &yd); if (rc) return rc;
     LOCK; ENGINE;
     const Fr z = load_fr(point);
     return pc_verify_core(e, v_srs, com, fr_pow_u(z, yd + 1), z, load_fr(eval), opening, rounds, accept);                      // mod.rs:380-386

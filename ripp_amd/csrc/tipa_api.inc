@@ -227,7 +227,31 @@ template <class T> static int32_t shard_gather_tail(Engine* e, const ShardCtx& s
     if ((rc = e->stage[3].send(buf.p, (size_t)sc.world * sizeof(T), e->stream))) return rc;
     return e->stage[3].wait();
 }
+// ---- small helpers of every caller below and of poly_commit_api.inc / tpc_api.inc ------------------------------------------------------------------
+static bool is_pow2(size_t v) { return v != 0 && !(v & (v - 1)); }
 static size_t log2_sz(size_t v) { size_t l = 0; while (((size_t)1 << l) < v) ++l; return l; }
+static std::vector<Fr> fr_powers(const Fr& s, size_t n) { std::vector<Fr> p(n); if (n) p[0] = Fr::one(); for (size_t i = 1; i < n; ++i) p[i] = mul(p[i - 1], s); return p; }      // structured_scalar_power
+static Fr fr_pow_u(Fr b, size_t k) { Fr r = Fr::one(); while (k) { if (k & 1) r = mul(r, b); b = mul(b, b); k >>= 1; } return r; }
+// the sqrt split of a univariate degree (poly_commit/mod.rs:299-306, transparent.rs:221-227): the skew factor is min(skew_cap, sqrt / 2); who / cite: the error text's
+static int32_t sqrt_split(size_t degree, size_t skew_cap, const char* who, const char* cite, size_t* x_degree, size_t* y_degree) {
+    if (!x_degree || !y_degree || degree >= ((size_t)1 << 62)) return RIPP_ERR_ARG;
+    const size_t v = degree + 1;
+    size_t lo = 0, hi = (size_t)1 << 31;                                                // floor(sqrt(v)) by bisection, then its ceiling
+    while (lo < hi) { const size_t mid = (lo + hi + 1) / 2; if (mid <= v / mid) lo = mid; else hi = mid - 1; }
+    const size_t s = lo * lo == v ? lo : lo + 1;
+    size_t sq = 1; while (sq < s) sq <<= 1;                                              // next_power_of_two
+    const size_t skew = std::min(skew_cap, sq / 2);
+    if (skew == 0) { set_err(std::string(who) + ": degree 0 has no split (the reference divides by a zero skew factor, " + cite + ")"); return RIPP_ERR_ARG; }
+    *x_degree = sq / skew - 1; *y_degree = sq * skew - 1;
+    return RIPP_OK;
+}
+// the end of a prover call: kernel times, wall time and (with_bytes) the resident device bytes into e->stats, a copy to the caller
+static int32_t finish_stats(Engine* e, double t_start, ripp_stats* st, bool with_bytes = true) {
+    e->collect_kernel_stats();
+    e->stats.total_ms = now_ms() - t_start; if (with_bytes) e->stats.device_bytes = g_dev_bytes.load(std::memory_order_relaxed);
+    if (st) *st = e->stats;
+    return RIPP_OK;
+}
 }  // extern "C++"
 
 // GIPA::_prove (gipa.rs:181-312) on vectors already resident (and normalised) in v.A (m_a), v.B (m_b), v.KA (ck_a), v.KB (ck_b).
@@ -390,10 +414,7 @@ API int32_t ripp_gipa_tipp_prove(const ripp_g1j* m_a, const ripp_g2j* m_b, const
     }
     const G1J ja = to_jac(ha), jkb = to_jac(hkb); const G2J jb = to_jac(hb), jka = to_jac(hka);
     std::memcpy(base_a, &ja, sizeof ja); std::memcpy(base_b, &jb, sizeof jb); std::memcpy(ck_base_a, &jka, sizeof jka); std::memcpy(ck_base_b, &jkb, sizeof jkb);
-    e->collect_kernel_stats();
-    e->stats.total_ms = now_ms() - t_start;
-    if (st) *st = e->stats;
-    return RIPP_OK;
+    return finish_stats(e, t_start, st, false);
 }
 
 // GIPA / TIPP across the communicator's ranks: every vector argument is this rank's shard (local j <-> global j * world + rank)
@@ -414,10 +435,7 @@ API int32_t ripp_gipa_tipp_prove_sharded(const ripp_g1j* m_a, const ripp_g2j* m_
     if ((rc = gipa_tipp_core(e, v, n_local, com_steps, transcript, ha, hb, hka, hkb, nullptr, sc))) return rc;
     const G1J ja = to_jac(ha), jkb = to_jac(hkb); const G2J jb = to_jac(hb), jka = to_jac(hka);
     std::memcpy(base_a, &ja, sizeof ja); std::memcpy(base_b, &jb, sizeof jb); std::memcpy(ck_base_a, &jka, sizeof jka); std::memcpy(ck_base_b, &jkb, sizeof jkb);
-    e->collect_kernel_stats();
-    e->stats.total_ms = now_ms() - t_start;
-    if (st) *st = e->stats;
-    return RIPP_OK;
+    return finish_stats(e, t_start, st, false);
 }
 
 // ---- TIPA: SRS handle, KZG openings (ip_proofs/src/tipa/mod.rs) ---------------------------------------------------------
@@ -444,7 +462,7 @@ extern "C++" {
 template <class F> static int32_t srs_powers(const Affine<F>& g, const ripp_fr* s_in, size_t num, void* out) {
     LOCK; ENGINE; if (!s_in || (num && !out)) return RIPP_ERR_ARG; if (!num) return RIPP_OK;
     Fr s; std::memcpy(&s, s_in, sizeof s);
-    std::vector<Fr> pw(num); pw[0] = Fr::one(); for (size_t i = 1; i < num; ++i) pw[i] = mul(pw[i - 1], s);
+    const std::vector<Fr> pw = fr_powers(s, num);
     DevBuf& jac = std::is_same<F, Fp>::value ? e->jacG1 : e->jacG2; DevBuf& aff = std::is_same<F, Fp>::value ? e->affG1 : e->affG2;
     int32_t rc; Fr* dk;
     if ((rc = upload<Fr>(e, e->tmpR, pw.data(), num, &dk)) || (rc = jac.reserve(num * sizeof(Jac<F>))) || (rc = aff.reserve(sizeof(Affine<F>)))) return rc;
@@ -562,17 +580,14 @@ API int32_t ripp_tipa_tipp_prove(const ripp_srs* srs, const ripp_g1j* m_a, const
     if ((rc = tipp_upload(e, v, m_a, m_b, ck_a, ck_b, n))) return rc;
     G1A ha, hkb; G2A hb, hka;
     if ((rc = gipa_tipp_core(e, v, n, com_steps, transcript, ha, hb, hka, hkb))) return rc;
-    size_t rounds = 0; while (((size_t)1 << rounds) < n) ++rounds;
+    const size_t rounds = log2_sz(n);
     Fr rs; std::memcpy(&rs, r_shift, sizeof rs);
     G2J oa; G1J ob; Fr c;
     if ((rc = tipp_kzg(e, srs, transcript, rounds, rs, hka, hkb, &oa, &ob, &c))) return rc;
     const G1J ja = to_jac(ha), jkb = to_jac(hkb); const G2J jb = to_jac(hb), jka = to_jac(hka);
     std::memcpy(base_a, &ja, sizeof ja); std::memcpy(base_b, &jb, sizeof jb); std::memcpy(final_ck_a, &jka, sizeof jka); std::memcpy(final_ck_b, &jkb, sizeof jkb);
     std::memcpy(opening_a, &oa, sizeof oa); std::memcpy(opening_b, &ob, sizeof ob); std::memcpy(kzg_challenge, &c, sizeof c);
-    e->collect_kernel_stats();
-    e->stats.total_ms = now_ms() - t_start;
-    if (st) *st = e->stats;
-    return RIPP_OK;
+    return finish_stats(e, t_start, st, false);
 }
 
 // ---- TIPAWithSSM (MIPP with a structured scalar vector), ip_proofs/src/tipa/structured_scalar_message.rs ------------------
@@ -592,6 +607,11 @@ struct SsmVecs {
     }
 };
 
+// the message of a second-tier argument: n projective G1 points of the host, normalised into v.A (v reserved for n)
+static int32_t ssm_load_message(Engine* e, SsmVecs& v, const ripp_g1j* m, size_t n) {
+    HIPCHK(hipMemcpyAsync(v.jac1.p, m, n * sizeof(G1J), hipMemcpyHostToDevice, e->stream));
+    return e->normalize_dev<Fp>(v.jac1.as<G1J>(), n, v.A.as<G1A>());
+}
 // GIPA<MultiexponentiationInnerProduct<G1>, AFGHO-G1, SSMPlaceholder, Identity<G1>>::_prove (gipa.rs:181-312): the rounds alone, which are all of
 // GIPAWithSSM::prove_with_structured_scalar_message (ssm.rs:66-84; the second tier of the transparent polynomial commitment, tpc_api.inc).
 // Per round: two pairing products share one line launch, two G1 MSMs over the halves.  Steps and transcript in ROUND order; *rounds_out = their number.
@@ -678,18 +698,14 @@ API int32_t ripp_tipa_ssm_prove(const ripp_srs* srs, const ripp_g1j* m_a, const 
     if (srs->num != 2 * n - 1) { set_err("SRS holds " + std::to_string(srs->num) + " powers, need 2n-1 = " + std::to_string(2 * n - 1)); return RIPP_ERR_ARG; }
     e->stats = ripp_stats{};
     const double t_start = now_ms();
-    SsmVecs v; int32_t rc; if ((rc = v.reserve(n))) return rc;
-    HIPCHK(hipMemcpyAsync(v.jac1.p, m_a, n * sizeof(G1J), hipMemcpyHostToDevice, e->stream)); if ((rc = e->normalize_dev<Fp>(v.jac1.as<G1J>(), n, v.A.as<G1A>()))) return rc;
+    SsmVecs v; int32_t rc; if ((rc = v.reserve(n)) || (rc = ssm_load_message(e, v, m_a, n))) return rc;
     HIPCHK(hipMemcpyAsync(v.jac2.p, ck_a, n * sizeof(G2J), hipMemcpyHostToDevice, e->stream)); if ((rc = e->normalize_dev<Fp2>(v.jac2.as<G2J>(), n, v.KA.as<G2A>()))) return rc;
     HIPCHK(hipMemcpyAsync(v.S.p, m_b, n * sizeof(Fr), hipMemcpyHostToDevice, e->stream)); if ((rc = e->sync())) return rc;
     G1A ha; Fr hs; G2A hka; G2J oa; Fr c;
     if ((rc = tipa_ssm_core(e, srs, v, n, com_gt, com_g1, transcript, ha, hs, hka, &oa, &c))) return rc;
     const G1J ja = to_jac(ha); const G2J jka = to_jac(hka);
     std::memcpy(base_a, &ja, sizeof ja); std::memcpy(base_b, &hs, sizeof hs); std::memcpy(final_ck_a, &jka, sizeof jka); std::memcpy(opening_a, &oa, sizeof oa); std::memcpy(kzg_challenge, &c, sizeof c);
-    e->collect_kernel_stats();
-    e->stats.total_ms = now_ms() - t_start;
-    if (st) *st = e->stats;
-    return RIPP_OK;
+    return finish_stats(e, t_start, st, false);
 }
 
 // ---- Groth16 aggregation: aggregate_proofs (ip_proofs/src/applications/groth16_aggregation.rs:77-160) ---------------------
@@ -813,10 +829,7 @@ static int32_t aggregate_impl(Engine* e, const ripp_srs* srs, const ripp_g1a* a,
         e->stats.kernel_miller_lines_launches += e2->stats.kernel_miller_lines_launches; e->stats.kernel_line_products_launches += e2->stats.kernel_line_products_launches;
         e->stats.pairs_lines += e2->stats.pairs_lines; e->stats.pairs_products += e2->stats.pairs_products;
     } else if ((rc = ssm_block(e))) return rc;
-    e->collect_kernel_stats();
-    e->stats.total_ms = now_ms() - t_start;
-    if (st) *st = e->stats;
-    return RIPP_OK;
+    return finish_stats(e, t_start, st, false);
 }
 
 API int32_t ripp_aggregate_proofs(const ripp_srs* srs, const ripp_g1a* a, const ripp_g2a* b, const ripp_g1a* c, size_t n, ripp_aggregate_proof* out, ripp_stats* st) {
@@ -917,6 +930,38 @@ static bool tipp_replay(const ripp_gt com[3], const ripp_gt* com_steps, size_t r
     out[0] = acc[0]; out[1] = acc[1]; out[2] = acc[2];
     return true;
 }
+// the same for the second-tier GIPAWithSSM instantiation (MultiexponentiationInnerProduct<G1>, AFGHO commitment): folds the steps into (ca, ct) = (com_a, com_t)
+static bool ssm_replay(Fp12& ca, G1J& ct, const ripp_gt* com_gt, const ripp_g1j* com_g1, size_t rounds, std::vector<Fr>& tr) {
+    tr.resize(rounds);
+    for (size_t k = 0; k < rounds; ++k) {                                                                                // gipa.rs:329-360
+        const Fp12 gt[2] = {load_gt(&com_gt[2 * k]), load_gt(&com_gt[2 * k + 1])};
+        if (!gt_in_cyclotomic(gt[0]) || !gt_in_cyclotomic(gt[1])) return false;                                          // not a GT element: reject
+        const G1A g1[2] = {to_affine(load_jac<Fp>(&com_g1[2 * k])), to_affine(load_jac<Fp>(&com_g1[2 * k + 1]))};
+        Fr c_inv; const Fr c = fs::gipa_ssm_challenge(k ? &tr[k - 1] : nullptr, gt, g1, c_inv);
+        auto f = host_pool().submit([&gt, c_inv]() { return gt_pow_host(gt[1], c_inv); });
+        ca = mul(ca, mul(gt_pow_host(gt[0], c), f.get()));
+        ct = add(add(ct, smul_host(g1[0], c)), smul_host(g1[1], c_inv));
+        tr[k] = c;
+    }
+    return true;
+}
+// exponents of _compute_final_commitment_keys (gipa.rs:365-399) by doubling over the reversed transcript (tr in ROUND order): powers of c^-1 for ck_a, of c for ck_b
+static std::vector<Fr> final_key_exponents(const std::vector<Fr>& tr, bool inverse) {
+    const size_t rounds = tr.size();
+    std::vector<Fr> ex((size_t)1 << rounds); ex[0] = Fr::one(); size_t cnt = 1;
+    for (size_t i = 0; i < rounds; ++i) {
+        const Fr c = inverse ? inv(tr[rounds - 1 - i]) : tr[rounds - 1 - i];
+        for (size_t j = 0; j < ((size_t)1 << i); ++j) ex[cnt + j] = mul(ex[j], c);
+        cnt += (size_t)1 << i;
+    }
+    return ex;
+}
+// b_base of the structured scalar vector (1, b, b^2, ..) (ssm.rs:108-114, 315-321); tr in ROUND order
+static Fr ssm_b_base(const std::vector<Fr>& tr, const Fr& scalar_b) {
+    Fr p2b = scalar_b, bb = Fr::one();
+    for (size_t i = 0; i < tr.size(); ++i) { bb = mul(bb, add(Fr::one(), mul(inv(tr[tr.size() - 1 - i]), p2b))); p2b = mul(p2b, p2b); }
+    return bb;
+}
 }  // extern "C++"
 
 API int32_t ripp_gipa_tipp_verify(const ripp_g2j* ck_a, const ripp_g1j* ck_b, size_t n, const ripp_gt com[3], const ripp_gt* com_steps, size_t rounds,
@@ -925,13 +970,7 @@ API int32_t ripp_gipa_tipp_verify(const ripp_g2j* ck_a, const ripp_g1j* ck_b, si
     if (!ck_a || !ck_b || !com || !base_a || !base_b || !accept || (rounds && !com_steps) || ((size_t)1 << rounds) != n) return RIPP_ERR_ARG;
     std::vector<Fr> tr; Fp12 bc[3];
     if (!tipp_replay(com, com_steps, rounds, tr, bc)) { *accept = 0; return RIPP_OK; }
-    // _compute_final_commitment_keys (gipa.rs:365-399) on the reversed transcript: exponent vectors by doubling, then one MSM per key
-    std::vector<Fr> ea(n), eb(n); ea[0] = Fr::one(); eb[0] = Fr::one(); size_t cnt = 1;
-    for (size_t i = 0; i < rounds; ++i) {
-        const Fr c = tr[rounds - 1 - i], ci = inv(c);
-        for (size_t j = 0; j < ((size_t)1 << i); ++j) { ea[cnt + j] = mul(ea[j], ci); eb[cnt + j] = mul(eb[j], c); }
-        cnt += (size_t)1 << i;
-    }
+    const std::vector<Fr> ea = final_key_exponents(tr, true), eb = final_key_exponents(tr, false);      // then one MSM per key
     ripp_g2j ka; ripp_g1j kb; int32_t rc;
     if ((rc = ripp_msm_g2_j(ck_a, n, reinterpret_cast<const ripp_fr*>(ea.data()), n, &ka))) return rc;
     if ((rc = ripp_msm_g1_j(ck_b, n, reinterpret_cast<const ripp_fr*>(eb.data()), n, &kb))) return rc;
@@ -965,9 +1004,26 @@ API int32_t ripp_tipa_tipp_verify(const ripp_verifier_srs* v_srs, const ripp_gt 
     return RIPP_OK;
 }
 
+// TIPAWithSSM::verify_with_structured_scalar_message (ssm.rs:270-331), engine in hand and the lock held by the caller (ripp_pc_verify runs it beside its KZG check):
+// replay, KZG check of the final key, base check
 static int32_t tipa_ssm_verify_core(Engine* e, const ripp_verifier_srs* v_srs, const ripp_gt* com_a, const ripp_g1j* com_t, const ripp_fr* scalar_b,
                                     const ripp_gt* com_gt, const ripp_g1j* com_g1, size_t rounds, const ripp_g1j* base_a,
-                                    const ripp_g2j* final_ck_a, const ripp_g2j* opening_a, int32_t* accept);
+                                    const ripp_g2j* final_ck_a, const ripp_g2j* opening_a, int32_t* accept) {
+    const VSrs v = load_vsrs(v_srs);
+    Fp12 ca = load_gt(com_a); G1J ct = load_jac<Fp>(com_t);
+    std::vector<Fr> trf;
+    if (!ssm_replay(ca, ct, com_gt, com_g1, rounds, trf)) { *accept = 0; return RIPP_OK; }
+    std::vector<Fr> tri(rounds); for (size_t i = 0; i < rounds; ++i) tri[i] = inv(trf[rounds - 1 - i]);
+    const G2J ka = load_jac<Fp2>(final_ck_a), oa = load_jac<Fp2>(opening_a); const G2A kaa = to_affine(ka);
+    const Fr c = fs::kzg_challenge(trf[rounds - 1], kaa, nullptr);                                                       // ssm.rs:289-303
+    bool ok_a = false; int32_t rc;
+    if ((rc = kzg_verify_g2(e, v, ka, oa, tri, Fr::one(), c, &ok_a))) return rc;                                         // ssm.rs:305-312
+    const G1A a = to_affine(load_jac<Fp>(base_a));
+    Fp12 e1; if ((rc = pairing_host_pts(e, {a}, {kaa}, &e1))) return rc;                                                 // ssm.rs:324-328
+    *accept = (ok_a && e1 == ca && eq(smul_host(a, ssm_b_base(trf, load_fr(scalar_b))), ct)) ? 1 : 0;                // ssm.rs:315-321
+    return RIPP_OK;
+}
+
 API int32_t ripp_tipa_ssm_verify(const ripp_verifier_srs* v_srs, const ripp_gt* com_a, const ripp_g1j* com_t, const ripp_fr* scalar_b,
                                  const ripp_gt* com_gt, const ripp_g1j* com_g1, size_t rounds, const ripp_g1j* base_a,
                                  const ripp_g2j* final_ck_a, const ripp_g2j* opening_a, int32_t* accept) {
@@ -975,42 +1031,13 @@ API int32_t ripp_tipa_ssm_verify(const ripp_verifier_srs* v_srs, const ripp_gt* 
     LOCK; ENGINE;
     return tipa_ssm_verify_core(e, v_srs, com_a, com_t, scalar_b, com_gt, com_g1, rounds, base_a, final_ck_a, opening_a, accept);
 }
-// the verifier itself, engine in hand and the lock held by the caller (ripp_pc_verify runs it beside its KZG check)
-static int32_t tipa_ssm_verify_core(Engine* e, const ripp_verifier_srs* v_srs, const ripp_gt* com_a, const ripp_g1j* com_t, const ripp_fr* scalar_b,
-                                    const ripp_gt* com_gt, const ripp_g1j* com_g1, size_t rounds, const ripp_g1j* base_a,
-                                    const ripp_g2j* final_ck_a, const ripp_g2j* opening_a, int32_t* accept) {
-    const VSrs v = load_vsrs(v_srs);
-    Fp12 ca = load_gt(com_a); G1J ct = load_jac<Fp>(com_t);
-    std::vector<Fr> trf(rounds);
-    for (size_t k = 0; k < rounds; ++k) {                                                                                // gipa.rs:329-360
-        const Fp12 gt[2] = {load_gt(&com_gt[2 * k]), load_gt(&com_gt[2 * k + 1])};
-        if (!gt_in_cyclotomic(gt[0]) || !gt_in_cyclotomic(gt[1])) { *accept = 0; return RIPP_OK; }
-        const G1A g1[2] = {to_affine(load_jac<Fp>(&com_g1[2 * k])), to_affine(load_jac<Fp>(&com_g1[2 * k + 1]))};
-        Fr c_inv; const Fr c = fs::gipa_ssm_challenge(k ? &trf[k - 1] : nullptr, gt, g1, c_inv);
-        auto f = host_pool().submit([&gt, c_inv]() { return gt_pow_host(gt[1], c_inv); });
-        ca = mul(ca, mul(gt_pow_host(gt[0], c), f.get()));
-        ct = add(add(ct, smul_host(g1[0], c)), smul_host(g1[1], c_inv));
-        trf[k] = c;
-    }
-    std::vector<Fr> tri(rounds); for (size_t i = 0; i < rounds; ++i) tri[i] = inv(trf[rounds - 1 - i]);
-    const G2J ka = load_jac<Fp2>(final_ck_a), oa = load_jac<Fp2>(opening_a); const G2A kaa = to_affine(ka);
-    const Fr c = fs::kzg_challenge(trf[rounds - 1], kaa, nullptr);                                                       // ssm.rs:289-303
-    bool ok_a = false; int32_t rc;
-    if ((rc = kzg_verify_g2(e, v, ka, oa, tri, Fr::one(), c, &ok_a))) return rc;                                         // ssm.rs:305-312
-    Fr p2b = load_fr(scalar_b), b_base = Fr::one();                                                                      // ssm.rs:315-321
-    for (size_t i = 0; i < rounds; ++i) { b_base = mul(b_base, add(Fr::one(), mul(tri[i], p2b))); p2b = mul(p2b, p2b); }
-    const G1A a = to_affine(load_jac<Fp>(base_a));
-    Fp12 e1; if ((rc = pairing_host_pts(e, {a}, {kaa}, &e1))) return rc;                                                 // ssm.rs:324-328
-    *accept = (ok_a && e1 == ca && eq(smul_host(a, b_base), ct)) ? 1 : 0;
-    return RIPP_OK;
-}
 
 API int32_t ripp_verify_aggregate_proof(const ripp_verifier_srs* v_srs, const ripp_groth16_vk* vk, const ripp_fr* public_inputs, size_t n, size_t m,
                                         const ripp_aggregate_proof* pf, int32_t* accept) {
     if (n < 2 || (n & (n - 1))) return RIPP_ERR_POW2;
     if (!v_srs || !vk || !vk->gamma_abc_g1 || (m && !public_inputs) || !pf || !accept) return RIPP_ERR_ARG;
     if (vk->gamma_abc_len != m + 1) { set_err("assert_eq!(vk.gamma_abc_g1.len(), public_inputs[0].len() + 1) (groth16_aggregation.rs:214)"); return RIPP_ERR_ARG; }
-    size_t rounds = 0; while (((size_t)1 << rounds) < n) ++rounds;
+    const size_t rounds = log2_sz(n);
     const Fr r = fs::aggregation_challenge(load_gt(&pf->com_a), load_gt(&pf->com_b), load_gt(&pf->com_c));             // :172-184
     int32_t ok_ab = 0, ok_c = 0, rc;
     const ripp_gt com_ab[3] = {pf->com_a, pf->com_b, pf->ip_ab};

@@ -1,53 +1,35 @@
-// Included by engine.hip inside its `extern "C"` block (after poly_commit_api.inc: it reuses its matrix uploads and fr_pow_u).
+// Included by engine.hip inside its `extern "C"` block (after poly_commit_api.inc: it builds on its two-tier core and matrix uploads).
 // ---- transparent polynomial commitments: ip_proofs/src/applications/poly_commit/transparent.rs on the device -------------------------------
 // BivariatePolynomialCommitment (:86-212) and UnivariatePolynomialCommitment (:214-330) behind a resident commitment-key handle, and the two
 // GIPAWithSSM arguments they are made of (tipa/structured_scalar_message.rs:56-128):
 //   second tier  GIPAWithSSM<MultiexponentiationInnerProduct<G1>, AFGHOCommitmentG1, IdentityCommitment<G1>>   the rounds of tipa_ssm_core (tipa_ssm_rounds)
 //   first tier   GIPAWithSSM<ScalarInnerProduct, PedersenCommitment<G1>, IdentityCommitment<Fr>>                the kernels of tpc.hpp
-// commit is one batched MSM over the resident first-tier keys and one pairing product; open keeps y_eval_coeffs on the device from the partial
-// evaluation through the last first-tier fold; the verifiers replay the transcripts on the host and run the two final-key MSMs on the resident keys.
+// commit, the head of open and the loading of the second tier are the two-tier core of poly_commit_api.inc on this handle's keys; open keeps y_eval_coeffs on
+// the device from the partial evaluation through the last first-tier fold; the verifiers replay the transcripts on the host (the second tier's with the
+// TIPAWithSSM verifier's ssm_replay, tipa_api.inc) and run the two final-key MSMs on the resident keys.
 // Every entry point takes LOCK once and calls the unlocked cores; none calls an exported function.
 
 extern "C++" {
-// the sqrt split with the transparent scheme's skew factor (transparent.rs:221-227)
-static int32_t tpc_univariate_degrees(size_t degree, size_t* x_degree, size_t* y_degree) {
-    if (degree >= ((size_t)1 << 62)) return RIPP_ERR_ARG;
-    const size_t v = degree + 1;
-    size_t lo = 0, hi = (size_t)1 << 31;
-    while (lo < hi) { const size_t mid = (lo + hi + 1) / 2; if (mid <= v / mid) lo = mid; else hi = mid - 1; }
-    const size_t s = lo * lo == v ? lo : lo + 1;
-    size_t sq = 1; while (sq < s) sq <<= 1;
-    const size_t skew = sq >= 8 ? 4 : sq / 2;
-    if (skew == 0) { set_err("ripp_tpc_univariate_degrees: degree 0 has no split (the reference divides by a zero skew factor, transparent.rs:223-226)"); return RIPP_ERR_ARG; }
-    *x_degree = sq / skew - 1; *y_degree = sq * skew - 1;
-    return RIPP_OK;
-}
-static bool tpc_pow2(size_t n) { return n >= 2 && !(n & (n - 1)); }
-static bool tpc_degrees_ok(size_t x_degree, size_t y_degree) { return x_degree < ((size_t)1 << 24) && y_degree < ((size_t)1 << 28) && tpc_pow2(x_degree + 1) && tpc_pow2(y_degree + 1); }
+static bool tpc_degrees_ok(size_t x_degree, size_t y_degree) { return x_degree < ((size_t)1 << 24) && y_degree < ((size_t)1 << 28) && x_degree && y_degree && is_pow2(x_degree + 1) && is_pow2(y_degree + 1); }
 static std::vector<double> g_tpc_round_ms;      // commitment + inner-product phase of every round of the last first-tier prover (ripp_tpc_round_ms)
 }  // extern "C++"
 
-API int32_t ripp_tpc_univariate_degrees(size_t degree, size_t* x_degree, size_t* y_degree) {
-    if (!x_degree || !y_degree) return RIPP_ERR_ARG;
-    return tpc_univariate_degrees(degree, x_degree, y_degree);
-}
+// UnivariatePolynomialCommitment::bivariate_degrees (transparent.rs:221-227); host only, needs no device
+API int32_t ripp_tpc_univariate_degrees(size_t degree, size_t* x_degree, size_t* y_degree) { return sqrt_split(degree, 4, "ripp_tpc_univariate_degrees", "transparent.rs:223-226", x_degree, y_degree); }
 
 // first_tier_ck (y_degree + 1 G1 points, affine, with the extended GLV form the batched MSM gathers from) and second_tier_ck (x_degree + 1 G2 points)
 struct ripp_tpc_ck { DevBuf k1, ext, k2; size_t nx = 0, ny = 0; };
 
 extern "C++" {
+static TwoTier tpc_key(const ripp_tpc_ck* s) { return {static_cast<const G1A*>(s->k1.p), static_cast<QAff<Fp>*>(s->ext.p), static_cast<const G2A*>(s->k2.p), s->nx, s->ny}; }
 static void tpc_ck_free(ripp_tpc_ck* s) { s->k1.release(); s->ext.release(); s->k2.release(); delete s; }
 static int32_t tpc_ck_alloc(size_t x_degree, size_t y_degree, ripp_tpc_ck** out) {
     ripp_tpc_ck* s = new ripp_tpc_ck(); s->nx = x_degree + 1; s->ny = y_degree + 1; int32_t rc;
     if ((rc = s->k1.reserve(s->ny * sizeof(G1A))) || (rc = s->ext.reserve(2 * s->ny * sizeof(G1A))) || (rc = s->k2.reserve(s->nx * sizeof(G2A)))) { tpc_ck_free(s); return rc; }
     *out = s; return RIPP_OK;
 }
-// the extended form once k1 is in place (as pc_srs_finish builds the one of the KZG powers)
-static int32_t tpc_ck_finish(Engine* e, ripp_tpc_ck* s) {
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_msm_extend_q<Fp>), dim3(nblk(s->ny, 256), 2), dim3(256), 0, e->stream, s->k1.as<G1A>(), (uint32_t)s->ny, 2, s->ext.as<QAff<Fp>>());
-    HIPCHK(hipGetLastError());
-    return e->sync();
-}
+// the extended form once k1 is in place
+static int32_t tpc_ck_finish(Engine* e, ripp_tpc_ck* s) { int32_t rc = two_tier_extend(e, tpc_key(s)); return rc ? rc : e->sync(); }
 // out[i] = (seed + i) * generator, normalised: the points of ripp_synth_g1 / ripp_synth_g2 (start = seed, first = 0, stride = 1)
 template <class F> static int32_t tpc_synth_dev(Engine* e, const Affine<F>& g, uint64_t seed, size_t n, Affine<F>* out) {
     DevBuf& jac = std::is_same<F, Fp>::value ? e->jacG1 : e->jacG2;
@@ -101,8 +83,6 @@ API int32_t ripp_tpc_round_ms(double* out, size_t cap) {
 }
 
 extern "C++" {
-static size_t tpc_log2(size_t n) { size_t r = 0; while (((size_t)1 << r) < n) ++r; return r; }
-static std::vector<Fr> tpc_powers(const Fr& s, size_t n) { std::vector<Fr> p(n); p[0] = Fr::one(); for (size_t i = 1; i < n; ++i) p[i] = mul(p[i - 1], s); return p; }      // structured_scalar_power
 static int32_t tpc_reserve_first(Engine* e, size_t n) {
     int32_t rc;
     for (DevBuf* b : {&e->tpc_m, &e->tpc_m2, &e->tpc_b, &e->tpc_b2}) if ((rc = b->reserve(n * sizeof(Fr)))) return rc;
@@ -170,23 +150,6 @@ static int32_t tpc_scalar_rounds(Engine* e, size_t n, const QAff<Fp>* ext0, ripp
     return RIPP_OK;
 }
 
-// exponents of _compute_final_commitment_keys (gipa.rs:365-399) for ck_a: by doubling over the reversed transcript (tr in ROUND order)
-static std::vector<Fr> tpc_key_exponents(const std::vector<Fr>& tr) {
-    const size_t rounds = tr.size(), n = (size_t)1 << rounds;
-    std::vector<Fr> ea(n); ea[0] = Fr::one(); size_t cnt = 1;
-    for (size_t i = 0; i < rounds; ++i) {
-        const Fr ci = inv(tr[rounds - 1 - i]);
-        for (size_t j = 0; j < ((size_t)1 << i); ++j) ea[cnt + j] = mul(ea[j], ci);
-        cnt += (size_t)1 << i;
-    }
-    return ea;
-}
-// b_base of the structured scalar vector (structured_scalar_message.rs:108-114)
-static Fr tpc_b_base(const std::vector<Fr>& tr, const Fr& scalar_b) {
-    Fr p2b = scalar_b, bb = Fr::one();
-    for (size_t i = 0; i < tr.size(); ++i) { bb = mul(bb, add(Fr::one(), mul(inv(tr[tr.size() - 1 - i]), p2b))); p2b = mul(p2b, p2b); }
-    return bb;
-}
 // sum_i ea[i] * keys[i] over device-resident keys
 template <class F> static int32_t tpc_final_key(Engine* e, const Affine<F>* dkeys, const std::vector<Fr>& ea, Jac<F>* out) {
     Fr* ds; int32_t rc;
@@ -210,103 +173,64 @@ static int32_t tpc_scalar_verify_core(Engine* e, const G1A* dkeys, size_t rounds
         tr[k] = c;
     }
     G1J ka; int32_t rc;
-    if ((rc = tpc_final_key<Fp>(e, dkeys, tpc_key_exponents(tr), &ka))) return rc;
+    if ((rc = tpc_final_key<Fp>(e, dkeys, final_key_exponents(tr, true), &ka))) return rc;
     // gipa_valid (:100-106, gipa.rs:401-415): the Pedersen commitment of a_base under the final key, the (empty) placeholder commitment, the product with the
     // proof's own r_base.1; base_valid (:108-125): the same with b_base recomputed from scalar_b
     const bool com_ok = eq(smul_host(to_affine(ka), base_a), ca);
     const bool gipa_valid = com_ok && mul(base_a, base_b) == ct;
-    const bool base_valid = com_ok && mul(base_a, tpc_b_base(tr, scalar_b)) == ct;
+    const bool base_valid = com_ok && mul(base_a, ssm_b_base(tr, scalar_b)) == ct;
     *ok = gipa_valid && base_valid; return RIPP_OK;
 }
-// the same for the second tier; dkeys: n = 2^rounds G2 keys on the device.  com = (com_a in GT, com_t in G1).
+// the same for the second tier; dkeys: n = 2^rounds G2 keys on the device.  com = (com_a in GT, com_t in G1).  Replay, final-key MSM, base checks.
 static int32_t tpc_mexp_verify_core(Engine* e, const G2A* dkeys, size_t rounds, const Fp12& com_a, const G1J& com_t, const Fr& scalar_b,
                                     const ripp_gt* com_gt, const ripp_g1j* com_g1, const G1J& base_a, const Fr& base_b, bool* ok) {
-    Fp12 ca = com_a; G1J ct = com_t;
-    std::vector<Fr> tr(rounds);
-    for (size_t k = 0; k < rounds; ++k) {
-        const Fp12 gt[2] = {load_gt(&com_gt[2 * k]), load_gt(&com_gt[2 * k + 1])};
-        if (!gt_in_cyclotomic(gt[0]) || !gt_in_cyclotomic(gt[1])) { *ok = false; return RIPP_OK; }                       // not a GT element: reject
-        const G1A g1[2] = {to_affine(load_jac<Fp>(&com_g1[2 * k])), to_affine(load_jac<Fp>(&com_g1[2 * k + 1]))};
-        Fr c_inv; const Fr c = fs::gipa_ssm_challenge(k ? &tr[k - 1] : nullptr, gt, g1, c_inv);
-        auto f = host_pool().submit([&gt, c_inv]() { return gt_pow_host(gt[1], c_inv); });
-        ca = mul(ca, mul(gt_pow_host(gt[0], c), f.get()));
-        ct = add(add(ct, smul_host(g1[0], c)), smul_host(g1[1], c_inv));
-        tr[k] = c;
-    }
+    Fp12 ca = com_a; G1J ct = com_t; std::vector<Fr> tr;
+    if (!ssm_replay(ca, ct, com_gt, com_g1, rounds, tr)) { *ok = false; return RIPP_OK; }
     G2J ka; int32_t rc;
-    if ((rc = tpc_final_key<Fp2>(e, dkeys, tpc_key_exponents(tr), &ka))) return rc;
+    if ((rc = tpc_final_key<Fp2>(e, dkeys, final_key_exponents(tr, true), &ka))) return rc;
     const G1A a = to_affine(base_a);
     Fp12 e1; if ((rc = pairing_host_pts(e, {a}, {to_affine(ka)}, &e1))) return rc;
     const bool com_ok = e1 == ca;
     const bool gipa_valid = com_ok && eq(smul_host(a, base_b), ct);
-    const bool base_valid = com_ok && eq(smul_host(a, tpc_b_base(tr, scalar_b)), ct);
+    const bool base_valid = com_ok && eq(smul_host(a, ssm_b_base(tr, scalar_b)), ct);
     *ok = gipa_valid && base_valid; return RIPP_OK;
 }
 
 static bool tpc_opening_ok(const ripp_tpc_opening* o) { return o && o->s_com_gt && o->s_com_g1 && o->s_transcript && o->f_com_g1 && o->f_com_fr && o->f_transcript; }
-static int32_t tpc_fits(const char* who, const ripp_tpc_ck* s, size_t rows, size_t cols) {
-    if (rows <= s->nx && cols <= s->ny) return RIPP_OK;
-    set_err(std::string(who) + ": " + std::to_string(rows) + " x " + std::to_string(cols) + " coefficients exceed the key's degrees (" + std::to_string(s->nx - 1) + ", " + std::to_string(s->ny - 1) + ")");
-    return RIPP_ERR_ARG;
-}
-static int32_t tpc_flat_fits(const char* who, const ripp_tpc_ck* s, size_t len) {
-    if (len <= s->nx * s->ny) return RIPP_OK;
-    set_err(std::string(who) + ": degree " + std::to_string(len - 1) + " exceeds the key's " + std::to_string(s->nx * s->ny - 1)); return RIPP_ERR_ARG;
-}
-// the x_degree + 1 Pedersen commitments of the rows (one batched MSM; missing rows are zero polynomials), then their AFGHO commitment (transparent.rs:101-127):
-// pc_commit_dev with the first-tier keys as bases and the second-tier keys as commitment key
-static int32_t tpc_commit_dev(Engine* e, const ripp_tpc_ck* s, const Fr* dcoef, size_t rows, size_t cols, size_t stride, ripp_gt* com, ripp_g1j* y_coms) {
-    ripp_tpc_ck* sm = const_cast<ripp_tpc_ck*>(s); int32_t rc;
-    if ((rc = e->pc_out.reserve(s->nx * sizeof(G1J))) || (rc = e->pc_aff.reserve(s->nx * sizeof(G1A)))) return rc;
-    HIPCHK(hipMemsetAsync(e->pc_out.p, 0, s->nx * sizeof(G1J), e->stream));            // Z = 0: the identity
-    if ((rc = e->msm_batch_dev(sm->k1.as<G1A>(), cols == s->ny ? sm->ext.as<QAff<Fp>>() : nullptr, dcoef, rows, cols, stride, e->pc_out.as<G1J>()))) return rc;
-    HIPCHK(hipMemcpyAsync(y_coms, e->pc_out.p, s->nx * sizeof(G1J), hipMemcpyDeviceToHost, e->stream));
-    if ((rc = e->normalize_dev<Fp>(e->pc_out.as<G1J>(), s->nx, e->pc_aff.as<G1A>()))) return rc;
-    if ((rc = e->sync())) return rc;
-    return pairing_product_dev(e, e->pc_aff.as<G1A>(), sm->k2.as<G2A>(), s->nx, com);
-}
 // BivariatePolynomialCommitment::open (transparent.rs:129-186) on a dense coefficient matrix in device memory
 static int32_t tpc_open_dev(Engine* e, const ripp_tpc_ck* s, const Fr* dcoef, size_t rows, size_t cols, size_t stride, const ripp_g1j* y_coms, const Fr& x, const Fr& y,
                             ripp_tpc_opening* o, ripp_fr* eval, ripp_stats* st) {
-    ripp_tpc_ck* sm = const_cast<ripp_tpc_ck*>(s); int32_t rc;
-    const size_t nx = s->nx, ny = s->ny;
-    e->stats = ripp_stats{};
-    const double t_start = now_ms();
-    const std::vector<Fr> xp = tpc_powers(x, nx), yp = tpc_powers(y, ny);                                               // :141-145, :170-174
-    SsmVecs v; if ((rc = v.reserve(nx)) || (rc = tpc_reserve_first(e, ny))) return rc;
-    HIPCHK(hipMemcpyAsync(v.S.p, xp.data(), nx * sizeof(Fr), hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(e->tpc_b.p, yp.data(), ny * sizeof(Fr), hipMemcpyHostToDevice, e->stream));
-    if ((rc = e->pc_yev.reserve(ny * sizeof(Fr)))) return rc;
-    hipLaunchKernelGGL(k_pc_partial_eval, dim3(nblk(ny, 256)), dim3(256), 0, e->stream, dcoef, (uint32_t)rows, (uint32_t)cols, stride, v.S.as<Fr>(), (uint32_t)ny, e->pc_yev.as<Fr>());   // :147-157
-    HIPCHK(hipGetLastError());
-    G1J yc; Fr ev;
-    if ((rc = e->msm_dev<Fp>(sm->k1.as<G1A>(), e->pc_yev.as<Fr>(), ny, &yc))) return rc;                                 // y_eval_comm (:158-159)
+    const TwoTier k = tpc_key(s); const size_t nx = k.nx, ny = k.ny; int32_t rc;
+    std::vector<Fr> yp;
+    SsmVecs v; G1J yc; Fr ev; double t_start;
+    rc = two_tier_open_prefix(e, k, v, dcoef, rows, cols, stride, x, &yc, &t_start, [&]() -> int32_t {                   // :141-159; behind the powers of x, those of y (:170-174)
+        int32_t r1 = tpc_reserve_first(e, ny); if (r1) return r1;
+        yp = fr_powers(y, ny);
+        HIPCHK(hipMemcpyAsync(e->tpc_b.p, yp.data(), ny * sizeof(Fr), hipMemcpyHostToDevice, e->stream));
+        return RIPP_OK; });
+    if (rc) return rc;
     if ((rc = fr_dot_dev(e, e->pc_yev.as<Fr>(), e->tpc_b.as<Fr>(), ny, &ev))) return rc;                               // p(x, y) = <y_eval_coeffs, powers of y>
     // second tier over (y_polynomial_comms, powers of x) under second_tier_ck (:161-168)
-    HIPCHK(hipMemcpyAsync(v.jac1.p, y_coms, nx * sizeof(G1J), hipMemcpyHostToDevice, e->stream)); if ((rc = e->normalize_dev<Fp>(v.jac1.as<G1J>(), nx, v.A.as<G1A>()))) return rc;
-    HIPCHK(hipMemcpyAsync(v.KA.p, sm->k2.p, nx * sizeof(G2A), hipMemcpyDeviceToDevice, e->stream)); if ((rc = e->sync())) return rc;
+    if ((rc = two_tier_load_second(e, k, v, y_coms))) return rc;
     G1A ha; Fr hs; G2A hka; size_t r2 = 0;
     if ((rc = tipa_ssm_rounds(e, v, nx, o->s_com_gt, o->s_com_g1, o->s_transcript, ha, hs, hka, &r2))) return rc;
     // first tier over (y_eval_coeffs, powers of y) under first_tier_ck (:176-183): the coefficients never left the device
     HIPCHK(hipMemcpyAsync(e->tpc_m.p, e->pc_yev.p, ny * sizeof(Fr), hipMemcpyDeviceToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(e->tpc_k.p, sm->k1.p, ny * sizeof(G1A), hipMemcpyDeviceToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->tpc_k.p, k.bases, ny * sizeof(G1A), hipMemcpyDeviceToDevice, e->stream));
     Fr fa, fb;
-    if ((rc = tpc_scalar_rounds(e, ny, sm->ext.as<QAff<Fp>>(), o->f_com_g1, o->f_com_fr, o->f_transcript, fa, fb))) return rc;
+    if ((rc = tpc_scalar_rounds(e, ny, k.ext, o->f_com_g1, o->f_com_fr, o->f_transcript, fa, fb))) return rc;
     const G1J ja = to_jac(ha);
     std::memcpy(&o->s_base_a, &ja, sizeof ja); std::memcpy(&o->s_base_b, &hs, sizeof hs); std::memcpy(&o->y_eval_comm, &yc, sizeof yc);
     std::memcpy(&o->f_base_a, &fa, sizeof fa); std::memcpy(&o->f_base_b, &fb, sizeof fb);
     if (eval) std::memcpy(eval, &ev, sizeof ev);
-    e->collect_kernel_stats();
-    e->stats.total_ms = now_ms() - t_start; e->stats.device_bytes = g_dev_bytes.load(std::memory_order_relaxed);
-    if (st) *st = e->stats;
-    return RIPP_OK;
+    return finish_stats(e, t_start, st);
 }
 // BivariatePolynomialCommitment::verify (transparent.rs:188-212)
 static int32_t tpc_verify_core(Engine* e, const ripp_tpc_ck* s, const ripp_gt* com, const Fr& x, const Fr& y, const Fr& eval, const ripp_tpc_opening* o, int32_t* accept) {
-    ripp_tpc_ck* sm = const_cast<ripp_tpc_ck*>(s); int32_t rc; bool ok2 = false, ok1 = false;
+    const TwoTier k = tpc_key(s); int32_t rc; bool ok2 = false, ok1 = false;
     const G1J yc = load_jac<Fp>(&o->y_eval_comm);
-    if ((rc = tpc_mexp_verify_core(e, sm->k2.as<G2A>(), tpc_log2(s->nx), load_gt(com), yc, x, o->s_com_gt, o->s_com_g1, load_jac<Fp>(&o->s_base_a), load_fr(&o->s_base_b), &ok2))) return rc;
-    if ((rc = tpc_scalar_verify_core(e, sm->k1.as<G1A>(), tpc_log2(s->ny), yc, eval, y, o->f_com_g1, o->f_com_fr, load_fr(&o->f_base_a), load_fr(&o->f_base_b), &ok1))) return rc;
+    if ((rc = tpc_mexp_verify_core(e, k.ck, log2_sz(k.nx), load_gt(com), yc, x, o->s_com_gt, o->s_com_g1, load_jac<Fp>(&o->s_base_a), load_fr(&o->s_base_b), &ok2))) return rc;
+    if ((rc = tpc_scalar_verify_core(e, k.bases, log2_sz(k.ny), yc, eval, y, o->f_com_g1, o->f_com_fr, load_fr(&o->f_base_a), load_fr(&o->f_base_b), &ok1))) return rc;
     *accept = (ok2 && ok1) ? 1 : 0; return RIPP_OK;
 }
 }  // extern "C++"
@@ -316,8 +240,8 @@ API int32_t ripp_tpc_commit(const ripp_tpc_ck* s, const ripp_fr* coeffs, size_t 
     if (!s || !com || !y_coms || (rows && cols && !coeffs) || stride < cols) return RIPP_ERR_ARG;
     LOCK; ENGINE;
     int32_t rc; Fr* dc;
-    if ((rc = tpc_fits("ripp_tpc_commit", s, rows, cols)) || (rc = pc_upload_matrix(e, coeffs, rows, cols, stride, &dc))) return rc;
-    return tpc_commit_dev(e, s, dc, rows, cols, cols, com, y_coms);
+    if ((rc = two_tier_fits("ripp_tpc_commit", "the key's degrees", tpc_key(s), rows, cols)) || (rc = pc_upload_matrix(e, coeffs, rows, cols, stride, &dc))) return rc;
+    return two_tier_commit(e, tpc_key(s), dc, rows, cols, cols, com, y_coms);
 }
 // BivariatePolynomialCommitment::open (transparent.rs:129-186)
 API int32_t ripp_tpc_open(const ripp_tpc_ck* s, const ripp_fr* coeffs, size_t rows, size_t cols, size_t stride, const ripp_g1j* y_coms, const ripp_fr* x, const ripp_fr* y,
@@ -325,7 +249,7 @@ API int32_t ripp_tpc_open(const ripp_tpc_ck* s, const ripp_fr* coeffs, size_t ro
     if (!s || !y_coms || !x || !y || !tpc_opening_ok(opening) || (rows && cols && !coeffs) || stride < cols) return RIPP_ERR_ARG;
     LOCK; ENGINE;
     int32_t rc; Fr* dc;
-    if ((rc = tpc_fits("ripp_tpc_open", s, rows, cols)) || (rc = pc_upload_matrix(e, coeffs, rows, cols, stride, &dc))) return rc;
+    if ((rc = two_tier_fits("ripp_tpc_open", "the key's degrees", tpc_key(s), rows, cols)) || (rc = pc_upload_matrix(e, coeffs, rows, cols, stride, &dc))) return rc;
     return tpc_open_dev(e, s, dc, rows, cols, cols, y_coms, load_fr(x), load_fr(y), opening, eval, st);
 }
 // BivariatePolynomialCommitment::verify (transparent.rs:188-212)
@@ -340,15 +264,15 @@ API int32_t ripp_tpc_commit_univariate(const ripp_tpc_ck* s, const ripp_fr* coef
     LOCK; ENGINE;
     len = pc_stripped_len(coeffs, len);
     int32_t rc; Fr* dc; size_t rows;
-    if ((rc = tpc_flat_fits("ripp_tpc_commit_univariate", s, len)) || (rc = pc_upload_flat(e, coeffs, len, s->ny, &rows, &dc))) return rc;
-    return tpc_commit_dev(e, s, dc, rows, rows ? s->ny : 0, s->ny, com, y_coms);
+    if ((rc = two_tier_flat_fits("ripp_tpc_commit_univariate", "the key's", tpc_key(s), len)) || (rc = pc_upload_flat(e, coeffs, len, s->ny, &rows, &dc))) return rc;
+    return two_tier_commit(e, tpc_key(s), dc, rows, rows ? s->ny : 0, s->ny, com, y_coms);
 }
 API int32_t ripp_tpc_open_univariate(const ripp_tpc_ck* s, const ripp_fr* coeffs, size_t len, const ripp_g1j* y_coms, const ripp_fr* point, ripp_tpc_opening* opening, ripp_fr* eval, ripp_stats* st) {
     if (!s || !y_coms || !point || !tpc_opening_ok(opening) || (len && !coeffs)) return RIPP_ERR_ARG;
     LOCK; ENGINE;
     len = pc_stripped_len(coeffs, len);
     int32_t rc; Fr* dc; size_t rows;
-    if ((rc = tpc_flat_fits("ripp_tpc_open_univariate", s, len)) || (rc = pc_upload_flat(e, coeffs, len, s->ny, &rows, &dc))) return rc;
+    if ((rc = two_tier_flat_fits("ripp_tpc_open_univariate", "the key's", tpc_key(s), len)) || (rc = pc_upload_flat(e, coeffs, len, s->ny, &rows, &dc))) return rc;
     const Fr z = load_fr(point);
     return tpc_open_dev(e, s, dc, rows, rows ? s->ny : 0, s->ny, y_coms, fr_pow_u(z, s->ny), z, opening, eval, st);               // :283-290
 }
@@ -363,7 +287,7 @@ API int32_t ripp_tpc_verify_univariate(const ripp_tpc_ck* s, const ripp_gt* com,
 // first tier: GIPAWithSSM<ScalarInnerProduct, PedersenCommitment<G1>, IdentityCommitment<Fr>>::prove_with_structured_scalar_message (ssm.rs:66-84)
 API int32_t ripp_gipa_ssm_scalar_prove(const ripp_fr* m, const ripp_fr* b, const ripp_g1a* ck, size_t n, ripp_g1j* com_g1, ripp_fr* com_fr, ripp_fr* transcript,
                                        ripp_fr* base_a, ripp_fr* base_b, ripp_stats* st) {
-    if (!tpc_pow2(n) || n > ((size_t)1 << 28)) return RIPP_ERR_POW2;
+    if (n < 2 || !is_pow2(n) || n > ((size_t)1 << 28)) return RIPP_ERR_POW2;
     if (!m || !b || !ck || !com_g1 || !com_fr || !transcript || !base_a || !base_b) return RIPP_ERR_ARG;
     LOCK; ENGINE;
     e->stats = ripp_stats{};
@@ -375,51 +299,45 @@ API int32_t ripp_gipa_ssm_scalar_prove(const ripp_fr* m, const ripp_fr* b, const
     Fr fa, fb;
     if ((rc = tpc_scalar_rounds(e, n, nullptr, com_g1, com_fr, transcript, fa, fb))) return rc;
     std::memcpy(base_a, &fa, sizeof fa); std::memcpy(base_b, &fb, sizeof fb);
-    e->collect_kernel_stats();
-    e->stats.total_ms = now_ms() - t_start; e->stats.device_bytes = g_dev_bytes.load(std::memory_order_relaxed);
-    if (st) *st = e->stats;
-    return RIPP_OK;
+    return finish_stats(e, t_start, st);
 }
 // ... ::verify_with_structured_scalar_message (ssm.rs:86-127); com = (com_a: Pedersen commitment of the message, com_t: the inner product)
 API int32_t ripp_gipa_ssm_scalar_verify(const ripp_g1a* ck, size_t n, const ripp_g1j* com_a, const ripp_fr* com_t, const ripp_fr* scalar_b,
                                         const ripp_g1j* com_g1, const ripp_fr* com_fr, const ripp_fr* base_a, const ripp_fr* base_b, int32_t* accept) {
-    if (!tpc_pow2(n) || n > ((size_t)1 << 28)) return RIPP_ERR_POW2;
+    if (n < 2 || !is_pow2(n) || n > ((size_t)1 << 28)) return RIPP_ERR_POW2;
     if (!ck || !com_a || !com_t || !scalar_b || !com_g1 || !com_fr || !base_a || !base_b || !accept) return RIPP_ERR_ARG;
     LOCK; ENGINE;
     G1A* dk; int32_t rc; bool ok = false;
     if ((rc = upload<G1A>(e, e->affG1, ck, n, &dk))) return rc;
-    if ((rc = tpc_scalar_verify_core(e, dk, tpc_log2(n), load_jac<Fp>(com_a), load_fr(com_t), load_fr(scalar_b), com_g1, com_fr, load_fr(base_a), load_fr(base_b), &ok))) return rc;
+    if ((rc = tpc_scalar_verify_core(e, dk, log2_sz(n), load_jac<Fp>(com_a), load_fr(com_t), load_fr(scalar_b), com_g1, com_fr, load_fr(base_a), load_fr(base_b), &ok))) return rc;
     *accept = ok ? 1 : 0; return RIPP_OK;
 }
 // second tier: GIPAWithSSM<MultiexponentiationInnerProduct<G1>, AFGHOCommitmentG1, IdentityCommitment<G1>>::prove_with_structured_scalar_message
 API int32_t ripp_gipa_ssm_mexp_prove(const ripp_g1j* m, const ripp_fr* b, const ripp_g2a* ck, size_t n, ripp_gt* com_gt, ripp_g1j* com_g1, ripp_fr* transcript,
                                      ripp_g1j* base_a, ripp_fr* base_b, ripp_stats* st) {
-    if (!tpc_pow2(n) || n > ((size_t)1 << 24)) return RIPP_ERR_POW2;
+    if (n < 2 || !is_pow2(n) || n > ((size_t)1 << 24)) return RIPP_ERR_POW2;
     if (!m || !b || !ck || !com_gt || !com_g1 || !transcript || !base_a || !base_b) return RIPP_ERR_ARG;
     LOCK; ENGINE;
     e->stats = ripp_stats{};
     const double t_start = now_ms();
     SsmVecs v; int32_t rc; if ((rc = v.reserve(n))) return rc;
-    HIPCHK(hipMemcpyAsync(v.jac1.p, m, n * sizeof(G1J), hipMemcpyHostToDevice, e->stream)); if ((rc = e->normalize_dev<Fp>(v.jac1.as<G1J>(), n, v.A.as<G1A>()))) return rc;
+    if ((rc = ssm_load_message(e, v, m, n))) return rc;
     HIPCHK(hipMemcpyAsync(v.KA.p, ck, n * sizeof(G2A), hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipMemcpyAsync(v.S.p, b, n * sizeof(Fr), hipMemcpyHostToDevice, e->stream)); if ((rc = e->sync())) return rc;
     G1A ha; Fr hs; G2A hka; size_t rounds = 0;
     if ((rc = tipa_ssm_rounds(e, v, n, com_gt, com_g1, transcript, ha, hs, hka, &rounds))) return rc;
     const G1J ja = to_jac(ha);
     std::memcpy(base_a, &ja, sizeof ja); std::memcpy(base_b, &hs, sizeof hs);
-    e->collect_kernel_stats();
-    e->stats.total_ms = now_ms() - t_start; e->stats.device_bytes = g_dev_bytes.load(std::memory_order_relaxed);
-    if (st) *st = e->stats;
-    return RIPP_OK;
+    return finish_stats(e, t_start, st);
 }
 // ... ::verify_with_structured_scalar_message; com = (com_a in GT: AFGHO commitment of the message, com_t in G1: the inner product)
 API int32_t ripp_gipa_ssm_mexp_verify(const ripp_g2a* ck, size_t n, const ripp_gt* com_a, const ripp_g1j* com_t, const ripp_fr* scalar_b,
                                       const ripp_gt* com_gt, const ripp_g1j* com_g1, const ripp_g1j* base_a, const ripp_fr* base_b, int32_t* accept) {
-    if (!tpc_pow2(n) || n > ((size_t)1 << 24)) return RIPP_ERR_POW2;
+    if (n < 2 || !is_pow2(n) || n > ((size_t)1 << 24)) return RIPP_ERR_POW2;
     if (!ck || !com_a || !com_t || !scalar_b || !com_gt || !com_g1 || !base_a || !base_b || !accept) return RIPP_ERR_ARG;
     LOCK; ENGINE;
     G2A* dk; int32_t rc; bool ok = false;
     if ((rc = upload<G2A>(e, e->affG2, ck, n, &dk))) return rc;
-    if ((rc = tpc_mexp_verify_core(e, dk, tpc_log2(n), load_gt(com_a), load_jac<Fp>(com_t), load_fr(scalar_b), com_gt, com_g1, load_jac<Fp>(base_a), load_fr(base_b), &ok))) return rc;
+    if ((rc = tpc_mexp_verify_core(e, dk, log2_sz(n), load_gt(com_a), load_jac<Fp>(com_t), load_fr(scalar_b), com_gt, com_g1, load_jac<Fp>(base_a), load_fr(base_b), &ok))) return rc;
     *accept = ok ? 1 : 0; return RIPP_OK;
 }

@@ -73,6 +73,65 @@ def _matrix(coeffs):
     return c, rows, cols, cols
 
 
+def _matrix_args(coeffs):
+    """the coefficient arguments of a bivariate entry point: coeffs, rows, cols, stride"""
+    c, rows, cols, stride = _matrix(coeffs)
+    return [_p(c), _sz(rows), _sz(cols), _sz(stride)]
+
+
+def _flat_args(polynomial):
+    """the coefficient arguments of a univariate entry point: the flat (n, 4) coefficient array and its length"""
+    c = np.ascontiguousarray(polynomial, dtype=np.uint64).reshape(-1, 4)
+    return [_p(c), _sz(len(c))]
+
+
+class _Handle:
+    """Owner of a resident key handle of the library.  The subclasses that `bind` makes name the library getter, its status check and the two exports
+    that read the degrees of a handle and free it."""
+    _lib = _check = _degrees = _destroy = None
+
+    def __init__(self, handle):
+        self._h = handle
+
+    def degrees(self):
+        x, y = ctypes.c_size_t(0), ctypes.c_size_t(0)
+        self._check(getattr(self._lib(), self._degrees)(self._h, ctypes.byref(x), ctypes.byref(y))); return x.value, y.value
+
+    def close(self):
+        if self._h:
+            getattr(self._lib(), self._destroy)(self._h); self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _commit(fn, key, coeff_args):
+    """`commit` of either scheme, bivariate or univariate -> (AFGHO commitment (72,), first-tier commitments of the y-polynomials (x_degree + 1, 18))"""
+    com = np.zeros(72, dtype=np.uint64); y_coms = np.zeros((key.degrees()[0] + 1, 18), dtype=np.uint64)
+    key._check(fn(key._h, *coeff_args, _p(com), _p(y_coms))); return com, y_coms
+
+
+def _open(fn, key, coeff_args, y_polynomial_comms, points, o):
+    """`open` of either scheme at (x, y) or (z,) into the opening `o` -> (proof dict, the value there (4,))"""
+    yc = np.ascontiguousarray(y_polynomial_comms, dtype=np.uint64).reshape(-1, 18)
+    assert len(yc) == key.degrees()[0] + 1
+    ev = np.zeros(4, dtype=np.uint64); st = RippStats()
+    key._check(fn(key._h, *coeff_args, _p(yc), *(_p(_a(q, 4)) for q in points), ctypes.byref(o.s), _p(ev), ctypes.byref(st)))
+    return o.to_proof(st.as_dict()), ev
+
+
+def _degrees_of(lib, check, export):
+    def univariate_degrees(degree):
+        """the sqrt split of a univariate degree (mod.rs:299-306, transparent.rs:221-227), computed by the library (needs no device)"""
+        x, y = ctypes.c_size_t(0), ctypes.c_size_t(0)
+        check(getattr(lib(), export)(_sz(degree), ctypes.byref(x), ctypes.byref(y)))
+        return x.value, y.value
+    return univariate_degrees
+
+
 def bind(lib=None):
     """The classes of this module over the library `lib()` returns (default: libripp_hip.so)."""
     lib = lib or _default_lib
@@ -97,11 +156,7 @@ def bind(lib=None):
             ctypes.memmove(getattr(s, k), arr.ctypes.data, arr.nbytes)
         return s
 
-    def univariate_degrees(degree):
-        """mod.rs:299-306, computed by the library (needs no device)"""
-        x, y = ctypes.c_size_t(0), ctypes.c_size_t(0)
-        check(lib().ripp_pc_univariate_degrees(_sz(degree), ctypes.byref(x), ctypes.byref(y)))
-        return x.value, y.value
+    univariate_degrees = _degrees_of(lib, check, "ripp_pc_univariate_degrees")
 
     def msm_g1_batch(bases, scalars, n=None):
         """out[r] = sum_i scalars[r][i] * bases[i]: bases (n, 12) affine, scalars (rows, cols, 4) with cols <= n -> (rows, 18) projective"""
@@ -111,11 +166,9 @@ def bind(lib=None):
         check(lib().ripp_msm_g1_batch_a(_p(bases), _sz(len(bases) if n is None else n), _p(sc), _sz(rows), _sz(cols), _sz(stride), _p(out)))
         return out
 
-    class PCSRS:
+    class PCSRS(_Handle):
         """`ripp_pc_srs`: the resident SRS of all three schemes."""
-
-        def __init__(self, handle):
-            self._h = handle
+        _lib, _check, _degrees, _destroy = staticmethod(lib), staticmethod(check), "ripp_pc_srs_degrees", "ripp_pc_srs_destroy"
 
         @staticmethod
         def setup(alpha, beta, x_degree, y_degree):
@@ -130,10 +183,6 @@ def bind(lib=None):
             check(lib().ripp_pc_srs_create(_p(kp), _sz(len(kp) - 1), _p(hb), _sz((len(hb) - 1) // 2), _p(_a(g_beta, 18)), _p(_a(h_alpha, 36)), ctypes.byref(h)))
             return PCSRS(h)
 
-        def degrees(self):
-            x, y = ctypes.c_size_t(0), ctypes.c_size_t(0)
-            check(lib().ripp_pc_srs_degrees(self._h, ctypes.byref(x), ctypes.byref(y))); return x.value, y.value
-
         def verifier_key(self):
             s = VerifierSRSStruct(); check(lib().ripp_pc_srs_verifier_key(self._h, ctypes.byref(s)))
             return {k: np.ctypeslib.as_array(getattr(s, k)).copy() for k in ("g", "h", "g_beta", "h_alpha")}
@@ -141,16 +190,6 @@ def bind(lib=None):
         def kzg_powers(self):
             out = np.zeros((self.degrees()[1] + 1, 12), dtype=np.uint64)
             check(lib().ripp_pc_srs_kzg_powers(self._h, _p(out))); return out
-
-        def close(self):
-            if self._h:
-                lib().ripp_pc_srs_destroy(self._h); self._h = ctypes.c_void_p()
-
-        def __del__(self):
-            try:
-                self.close()
-            except Exception:
-                pass
 
     class Opening:
         """Owner of a PCOpeningStruct and of its step arrays."""
@@ -221,19 +260,12 @@ def bind(lib=None):
         @staticmethod
         def commit(srs, coeffs):
             """-> (AFGHO commitment (72,), KZG commitments of the y-polynomials (x_degree + 1, 18))"""
-            c, rows, cols, stride = _matrix(coeffs)
-            com = np.zeros(72, dtype=np.uint64); y_coms = np.zeros((srs.degrees()[0] + 1, 18), dtype=np.uint64)
-            check(lib().ripp_pc_commit(srs._h, _p(c), _sz(rows), _sz(cols), _sz(stride), _p(com), _p(y_coms))); return com, y_coms
+            return _commit(lib().ripp_pc_commit, srs, _matrix_args(coeffs))
 
         @staticmethod
         def open(srs, coeffs, y_polynomial_comms, point):
             """-> (proof dict, p(x, y) (4,))"""
-            c, rows, cols, stride = _matrix(coeffs)
-            yc = np.ascontiguousarray(y_polynomial_comms, dtype=np.uint64).reshape(-1, 18)
-            assert len(yc) == srs.degrees()[0] + 1
-            o = Opening(_rounds(srs)); ev = np.zeros(4, dtype=np.uint64); st = RippStats()
-            check(lib().ripp_pc_open(srs._h, _p(c), _sz(rows), _sz(cols), _sz(stride), _p(yc), _p(_a(point[0], 4)), _p(_a(point[1], 4)), ctypes.byref(o.s), _p(ev), ctypes.byref(st)))
-            return o.to_proof(st.as_dict()), ev
+            return _open(lib().ripp_pc_open, srs, _matrix_args(coeffs), y_polynomial_comms, point[:2], Opening(_rounds(srs)))
 
         @staticmethod
         def verify(v_srs, com, point, eval, proof):
@@ -252,19 +284,12 @@ def bind(lib=None):
 
         @staticmethod
         def commit(srs, polynomial):
-            c = np.ascontiguousarray(polynomial, dtype=np.uint64).reshape(-1, 4)
-            com = np.zeros(72, dtype=np.uint64); y_coms = np.zeros((srs.degrees()[0] + 1, 18), dtype=np.uint64)
-            check(lib().ripp_pc_commit_univariate(srs._h, _p(c), _sz(len(c)), _p(com), _p(y_coms))); return com, y_coms
+            return _commit(lib().ripp_pc_commit_univariate, srs, _flat_args(polynomial))
 
         @staticmethod
         def open(srs, polynomial, y_polynomial_comms, point):
             """-> (proof dict, p(point) (4,))"""
-            c = np.ascontiguousarray(polynomial, dtype=np.uint64).reshape(-1, 4)
-            yc = np.ascontiguousarray(y_polynomial_comms, dtype=np.uint64).reshape(-1, 18)
-            assert len(yc) == srs.degrees()[0] + 1
-            o = Opening(_rounds(srs)); ev = np.zeros(4, dtype=np.uint64); st = RippStats()
-            check(lib().ripp_pc_open_univariate(srs._h, _p(c), _sz(len(c)), _p(yc), _p(_a(point, 4)), ctypes.byref(o.s), _p(ev), ctypes.byref(st)))
-            return o.to_proof(st.as_dict()), ev
+            return _open(lib().ripp_pc_open_univariate, srs, _flat_args(polynomial), y_polynomial_comms, [point], Opening(_rounds(srs)))
 
         @staticmethod
         def verify(v_srs, max_degree, com, point, eval, proof):
@@ -302,17 +327,11 @@ def _bind_transparent(lib, check):
     def log2(n):
         return n.bit_length() - 1
 
-    def univariate_degrees(degree):
-        """transparent.rs:221-227, computed by the library (needs no device)"""
-        x, y = ctypes.c_size_t(0), ctypes.c_size_t(0)
-        check(lib().ripp_tpc_univariate_degrees(_sz(degree), ctypes.byref(x), ctypes.byref(y)))
-        return x.value, y.value
+    univariate_degrees = _degrees_of(lib, check, "ripp_tpc_univariate_degrees")
 
-    class CK:
+    class CK(_Handle):
         """`ripp_tpc_ck`: the resident commitment key (first-tier G1 keys with their extended form, second-tier G2 keys)."""
-
-        def __init__(self, handle):
-            self._h = handle
+        _lib, _check, _degrees, _destroy = staticmethod(lib), staticmethod(check), "ripp_tpc_ck_degrees", "ripp_tpc_ck_destroy"
 
         @staticmethod
         def setup(seed_g1, seed_g2, x_degree, y_degree):
@@ -328,25 +347,11 @@ def _bind_transparent(lib, check):
             check(lib().ripp_tpc_ck_create(_p(k1), _sz(len(k1) - 1), _p(k2), _sz(len(k2) - 1), ctypes.byref(h)))
             return CK(h)
 
-        def degrees(self):
-            x, y = ctypes.c_size_t(0), ctypes.c_size_t(0)
-            check(lib().ripp_tpc_ck_degrees(self._h, ctypes.byref(x), ctypes.byref(y))); return x.value, y.value
-
         def keys(self):
             """-> (first_tier_ck (y_degree + 1, 12), second_tier_ck (x_degree + 1, 24)), affine"""
             xd, yd = self.degrees()
             k1 = np.zeros((yd + 1, 12), dtype=np.uint64); k2 = np.zeros((xd + 1, 24), dtype=np.uint64)
             check(lib().ripp_tpc_ck_keys(self._h, _p(k1), _p(k2))); return k1, k2
-
-        def close(self):
-            if self._h:
-                lib().ripp_tpc_ck_destroy(self._h); self._h = ctypes.c_void_p()
-
-        def __del__(self):
-            try:
-                self.close()
-            except Exception:
-                pass
 
     class Opening:
         """Owner of a TPCOpeningStruct and of its step arrays."""
@@ -435,19 +440,12 @@ def _bind_transparent(lib, check):
         @staticmethod
         def commit(ck, coeffs):
             """-> (AFGHO commitment (72,), Pedersen commitments of the y-polynomials (x_degree + 1, 18))"""
-            c, rows, cols, stride = _matrix(coeffs)
-            com = np.zeros(72, dtype=np.uint64); y_coms = np.zeros((ck.degrees()[0] + 1, 18), dtype=np.uint64)
-            check(lib().ripp_tpc_commit(ck._h, _p(c), _sz(rows), _sz(cols), _sz(stride), _p(com), _p(y_coms))); return com, y_coms
+            return _commit(lib().ripp_tpc_commit, ck, _matrix_args(coeffs))
 
         @staticmethod
         def open(ck, coeffs, y_polynomial_comms, point):
             """-> (proof dict, p(x, y) (4,))"""
-            c, rows, cols, stride = _matrix(coeffs)
-            yc = np.ascontiguousarray(y_polynomial_comms, dtype=np.uint64).reshape(-1, 18)
-            assert len(yc) == ck.degrees()[0] + 1
-            o = _opening(ck); ev = np.zeros(4, dtype=np.uint64); st = RippStats()
-            check(lib().ripp_tpc_open(ck._h, _p(c), _sz(rows), _sz(cols), _sz(stride), _p(yc), _p(_a(point[0], 4)), _p(_a(point[1], 4)), ctypes.byref(o.s), _p(ev), ctypes.byref(st)))
-            return o.to_proof(st.as_dict()), ev
+            return _open(lib().ripp_tpc_open, ck, _matrix_args(coeffs), y_polynomial_comms, point[:2], _opening(ck))
 
         @staticmethod
         def verify(ck, com, point, eval, proof):
@@ -466,19 +464,12 @@ def _bind_transparent(lib, check):
 
         @staticmethod
         def commit(ck, polynomial):
-            c = np.ascontiguousarray(polynomial, dtype=np.uint64).reshape(-1, 4)
-            com = np.zeros(72, dtype=np.uint64); y_coms = np.zeros((ck.degrees()[0] + 1, 18), dtype=np.uint64)
-            check(lib().ripp_tpc_commit_univariate(ck._h, _p(c), _sz(len(c)), _p(com), _p(y_coms))); return com, y_coms
+            return _commit(lib().ripp_tpc_commit_univariate, ck, _flat_args(polynomial))
 
         @staticmethod
         def open(ck, polynomial, y_polynomial_comms, point):
             """-> (proof dict, p(point) (4,))"""
-            c = np.ascontiguousarray(polynomial, dtype=np.uint64).reshape(-1, 4)
-            yc = np.ascontiguousarray(y_polynomial_comms, dtype=np.uint64).reshape(-1, 18)
-            assert len(yc) == ck.degrees()[0] + 1
-            o = _opening(ck); ev = np.zeros(4, dtype=np.uint64); st = RippStats()
-            check(lib().ripp_tpc_open_univariate(ck._h, _p(c), _sz(len(c)), _p(yc), _p(_a(point, 4)), ctypes.byref(o.s), _p(ev), ctypes.byref(st)))
-            return o.to_proof(st.as_dict()), ev
+            return _open(lib().ripp_tpc_open_univariate, ck, _flat_args(polynomial), y_polynomial_comms, [point], _opening(ck))
 
         @staticmethod
         def verify(ck, com, point, eval, proof):

@@ -467,6 +467,18 @@ def test_gipa_tipp_prove_vs_oracle(engine, orc, n):
         assert not engine.GIPA_TIPP.verify(ck_a, ck_b, com, raw["round_order_steps"], (proof["r_base"][0], aux["ck_base"][0]))
 
 
+@pytest.mark.parametrize("n", [2, 4])
+def test_gipa_tipp_verify_final_keys(engine, orc, n):
+    """ripp_gipa_tipp_verify derives both final keys from one exponent function (powers of c^-1 for ck_a, of c for ck_b): it accepts the prover's proof at one
+    round and at two, and rejects it with base_a replaced."""
+    m_a, m_b = orc.blind_g1(orc.gen_g1(11, n), 1), orc.blind_g2(orc.gen_g2(22, n), 2)
+    ck_a, ck_b = orc.blind_g2(orc.gen_g2(33, n), 3), orc.blind_g1(orc.gen_g1(44, n), 4)
+    proof, aux, raw = engine.GIPA_TIPP.prove_with_aux(m_a, m_b, ck_a, ck_b)
+    com = [engine.AFGHOCommitmentG1.commit(ck_a, m_a), engine.AFGHOCommitmentG2.commit(ck_b, m_b), engine.PairingInnerProduct.inner_product(m_a, m_b)]
+    assert engine.GIPA_TIPP.verify(ck_a, ck_b, com, raw["round_order_steps"], proof["r_base"])
+    assert not engine.GIPA_TIPP.verify(ck_a, ck_b, com, raw["round_order_steps"], (aux["ck_base"][1], proof["r_base"][1]))
+
+
 def test_c_abi_demo_program(engine, tmp_path):
     """examples/c_abi_demo.c: a C99 program using only include/ripp_hip.h proves and verifies a 2^10 statement, rejects a tampered proof
     and sees the reference's length error as a status code."""

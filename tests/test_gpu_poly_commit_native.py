@@ -219,9 +219,12 @@ def _cmp_proof(orc, got, exp):
     assert _same_g1(orc, got["y_eval_comm"], exp["y_eval_comm"]) and _same_g1(orc, got["kzg_proof"], exp["kzg_proof"])
 
 
-@pytest.mark.parametrize("x_degree,y_degree,n_rows", [(7, 7, 8), (1, 3, 2), (3, 15, 3)])
-def test_bivariate_poly_commit(engine, orc, P, N, x_degree, y_degree, n_rows):
-    """mod.rs:405-443; n_rows < x_degree + 1 exercises the zero-polynomial padding (mod.rs:183-187)"""
+@pytest.mark.parametrize("x_degree,y_degree,n_rows,n_cols", [pytest.param(7, 7, 8, 8, id="7-7-8"), pytest.param(1, 3, 2, 4, id="1-3-2"), pytest.param(3, 15, 3, 16, id="3-15-3"),
+                                                            pytest.param(1, 7, 2, 5, id="1-7-2-cols5")])
+def test_bivariate_poly_commit(engine, orc, P, N, x_degree, y_degree, n_rows, n_cols):
+    """mod.rs:405-443; n_rows < x_degree + 1 exercises the zero-polynomial padding (mod.rs:183-187).  The three cases of the shared commit core: n_cols == y_degree + 1
+    (the batched MSM gathers from the handle's resident extended bases), n_cols < y_degree + 1 (it rebuilds them for the shorter rows), n_rows < x_degree + 1 (missing
+    rows are the identity)."""
     import poly_commit_oracle as PC
     B = N.BivariatePolynomialCommitment
     rng = random.Random(x_degree * 100 + y_degree)
@@ -230,18 +233,18 @@ def test_bivariate_poly_commit(engine, orc, P, N, x_degree, y_degree, n_rows):
     srs = B.setup(P.frs([alpha])[0], P.frs([beta])[0], x_degree, y_degree); s = PC.bi_setup(alpha, beta, x_degree, y_degree)
     assert srs.degrees() == (x_degree, y_degree) and np.array_equal(srs.kzg_powers(), s["kzg"])
     v_srs = srs.verifier_key()
-    ys = [[rng.randrange(orc.R) for _ in range(y_degree + 1)] for _ in range(n_rows)]
+    ys = [[rng.randrange(orc.R) for _ in range(n_cols)] for _ in range(n_rows)]
     coeffs = np.stack([P.frs(r) for r in ys])
     com, coms = B.commit(srs, coeffs); ecom, ecoms = PC.bi_commit(s, ys)
     assert np.array_equal(com, ecom) and _same_g1(orc, coms, ecoms)
-    wide = np.zeros((n_rows, y_degree + 4, 4), dtype=np.uint64); wide[:, :y_degree + 1] = coeffs; wide[:, y_degree + 1:] = 0xABCDEF       # stride > cols: the tail is never read
-    com2, coms2 = B.commit(srs, wide[:, :y_degree + 1]); assert np.array_equal(com2, com) and _same_g1(orc, coms2, coms)
+    wide = np.zeros((n_rows, n_cols + 3, 4), dtype=np.uint64); wide[:, :n_cols] = coeffs; wide[:, n_cols:] = 0xABCDEF       # stride > cols: the tail is never read
+    com2, coms2 = B.commit(srs, wide[:, :n_cols]); assert np.array_equal(com2, com) and _same_g1(orc, coms2, coms)
     point = (rng.randrange(orc.R), rng.randrange(orc.R)); fpoint = (P.frs([point[0]])[0], P.frs([point[1]])[0])
     proof, val = B.open(srs, coeffs, coms, fpoint); eproof = PC.bi_open(s, ys, ecoms, point)
     _cmp_proof(orc, proof, eproof)                                                         # every member, as test_gpu_poly_commit._cmp_ssm does
     ival = _int(orc, val); assert ival == PC.bi_evaluate(ys, point)
     # two opens in a row on one handle give identical bytes
-    proof2, val2 = B.open(srs, wide[:, :y_degree + 1], coms, fpoint)
+    proof2, val2 = B.open(srs, wide[:, :n_cols], coms, fpoint)
     assert np.array_equal(val2, val) and all(np.array_equal(proof2["ip_proof"][k], proof["ip_proof"][k]) for k in ("com_gt", "com_g1", "tr", "base_a", "base_b", "final_ck_a", "opening_a", "kzg_c"))
     assert np.array_equal(proof2["y_eval_comm"], proof["y_eval_comm"]) and np.array_equal(proof2["kzg_proof"], proof["kzg_proof"])
     assert B.verify(v_srs, com, fpoint, val, proof)

@@ -276,6 +276,48 @@ def test_second_tier_against_the_oracle(engine, orc, P, T, n, variant):
     assert not T.mexp_verify(ck, (com[0], orc.to_jac_g1(engine.synth_g1(6, 1))[0]), fs, proof)
 
 
+def _in_cyclotomic(orc, gt):
+    """x^(p^4 - p^2 + 1) == 1 for a (72,) limb GT value, in the big-integer model (tests/model/bls381_model.py)"""
+    import bls381_model as M
+    import tipa_model as TM
+    x = TM.gt_from_tower([orc.limbs_to_fp(gt[6 * i:6 * i + 6]) for i in range(12)])
+    return M.f12pow(x, M.P ** 4 - M.P ** 2 + 1) == M.F12_ONE
+
+
+@pytest.mark.parametrize("n", [2, 4])
+def test_second_tier_rounds_are_one_function_for_both_callers(engine, orc, P, T, n):
+    """ripp_gipa_ssm_mexp_prove (the transparent scheme's second tier) and ripp_tipa_ssm_prove (TIPAWithSSM) run the same rounds on the same loaded message: on one
+    message, one structured scalar vector and one G2 key (the even powers of an SRS of 2 n - 1 powers, as ripp_amd.api builds for TIPAWithSSM) they return identical
+    com_gt, com_g1, transcript, base_a and base_b bytes, n = 2 (one round, no previous challenge) and n = 4 (the chained challenge).  Both verifiers replay the
+    transcript with one function: both accept, and both reject a GT step member outside the cyclotomic subgroup."""
+    import helpers as h
+    osrs = h.make_srs(n, 0x5eed + n, 0xfeed + n); srs = engine.SRS(osrs[0], osrs[1])
+    ck_j, _ = h.commitment_keys(osrs); ck = engine.normalize_batch_g2(ck_j)
+    msg = orc.blind_g1(orc.gen_g1(13, n), 3)
+    s = 0x5eed5eed5eed5eed5eed5eed5eed5eed5eed % orc.R; fs = P.frs([s])[0]
+    b = P.frs([pow(s, i, orc.R) for i in range(n)])
+    proof, tr = T.mexp_prove(msg, b, ck)
+    tipa = engine.TIPAWithSSM.prove_with_structured_scalar_message(srs, (msg, b), (ck_j,))
+    steps = proof["r_commitment_steps"][::-1]                                              # ROUND order, as the TIPAWithSSM arrays
+    gt = np.stack([side[0] for st in steps for side in st]); g1 = np.stack([side[2][0] for st in steps for side in st])
+    assert len(tr) == n.bit_length() - 1
+    assert gt.tobytes() == tipa["com_gt"].tobytes() and g1.tobytes() == tipa["com_g1"].tobytes() and tr.tobytes() == tipa["tr"].tobytes()
+    assert np.asarray(proof["r_base"][0]).tobytes() == tipa["base_a"].tobytes() and np.asarray(proof["r_base"][1]).tobytes() == tipa["base_b"].tobytes()
+    com = (engine.AFGHOCommitmentG1.commit(ck_j, msg), engine.MultiexponentiationInnerProductG1.inner_product(msg, b))
+    g, hh, g_beta, _ = h.verifier_srs(osrs); vk = {"g": g, "h": hh, "g_beta": g_beta, "h_alpha": osrs[3]}
+    assert T.mexp_verify(ck, com, fs, proof)
+    assert engine.TIPAWithSSM.verify_with_structured_scalar_message(vk, com, fs, tipa)
+    # a GT member with one limb incremented: the model shows that it has left the cyclotomic subgroup (and that the honest member is in it)
+    k = 2 * len(steps) - 1
+    off = tipa["com_gt"].copy(); off[k, 0] += np.uint64(1)
+    assert _in_cyclotomic(orc, tipa["com_gt"][k]) and not _in_cyclotomic(orc, off[k])
+    assert not engine.TIPAWithSSM.verify_with_structured_scalar_message(vk, com, fs, dict(tipa, com_gt=off))
+    zero = np.zeros(4, dtype=np.uint64)
+    bad = [((off[2 * r], zero, [g1[2 * r]]), (off[2 * r + 1], zero, [g1[2 * r + 1]])) for r in range(len(steps))][::-1]
+    assert not T.mexp_verify(ck, com, fs, {"r_commitment_steps": bad, "r_base": proof["r_base"]})
+    srs.close()
+
+
 # ---------------------------------------------------------------------------------------------------------------- bivariate
 def _cmp_opening(orc, proof, eproof):
     """native opening against the oracle's tr_open, every member"""
