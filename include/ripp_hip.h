@@ -511,9 +511,31 @@ int32_t ripp_gipa_ssm_mexp_prove(const ripp_g1j* m, const ripp_fr* b, const ripp
                                  ripp_fr* transcript /* [r] */, ripp_g1j* base_a, ripp_fr* base_b, ripp_stats* stats);
 int32_t ripp_gipa_ssm_mexp_verify(const ripp_g2a* ck, size_t n, const ripp_gt* com_a, const ripp_g1j* com_t, const ripp_fr* scalar_b,
                                   const ripp_gt* com_gt, const ripp_g1j* com_g1, const ripp_g1j* base_a, const ripp_fr* base_b, int32_t* accept);
+/* GIPA with a COMMITTED scalar vector (MIPP): GIPA<MultiexponentiationInnerProduct<G1>, AFGHOCommitmentG1, PedersenCommitment<G1>, IdentityCommitment<G1>, Blake2b>.
+ * GIPA::prove_with_aux / _prove (gipa.rs:162-312), instantiation of gipa.rs:499-530 and benches/benches/gipa.rs case 2.
+ * m_a in G1, m_b in Fr (arbitrary), ck_a in G2 (AFGHO), ck_b in G1 (Pedersen).  n a power of two >= 2 (RIPP_ERR_POW2; narrower than the
+ * reference like ripp_gipa_ssm_*).  Steps in ROUND order:
+ *   com_gt[r][2]  = (com_1.0, com_2.0)   AFGHO commitments of the m_a halves
+ *   com_ped[r][2] = (com_1.1, com_2.1)   Pedersen commitments of the m_b halves
+ *   com_ip[r][2]  = (com_1.2[0], com_2.2[0])   the inner products
+ * base = r_base, ck_base = aux.ck_base; projective members are any representative.
+ * Single device: ripp_config.n_devices and the communicator are ignored.  Argument errors (a NULL pointer other than stats: RIPP_ERR_ARG; a bad length:
+ * RIPP_ERR_POW2) are reported before the device is looked for and nothing is allocated on a failure path.  ripp_stats as for ripp_gipa_ssm_mexp_prove:
+ * miller_products_ms (the pairing products and, beside them, the round's four G1 MSMs), fold_ms, host_ms, total_ms.
+ * RIPP_GIPA_MEXP_BATCH_MIN (environment) moves the vector length from which a round's four G1 MSMs run as ONE four-row pass of the batched MSM pipeline
+ * instead of four single MSMs (profiles/gipa_mexp_ab.txt has the measurement behind the default). */
+int32_t ripp_gipa_mexp_prove(const ripp_g1j* m_a, const ripp_fr* m_b, const ripp_g2a* ck_a, const ripp_g1a* ck_b, size_t n,
+                             ripp_gt* com_gt, ripp_g1j* com_ped, ripp_g1j* com_ip, ripp_fr* transcript,
+                             ripp_g1j* base_a, ripp_fr* base_b, ripp_g2j* ck_base_a, ripp_g1j* ck_base_b, ripp_stats* stats);
+/* GIPA::verify (gipa.rs:135-160, 322-415): transcript replay on the host, BOTH final keys as device MSMs, base check.  com = (com_a in GT: AFGHO commitment of
+ * m_a, com_b in G1: Pedersen commitment of m_b, com_t in G1: <m_a, m_b>).  Steps that are no group elements give accept = 0 with RIPP_OK.  Single device. */
+int32_t ripp_gipa_mexp_verify(const ripp_g2a* ck_a, const ripp_g1a* ck_b, size_t n,
+                              const ripp_gt* com_a, const ripp_g1j* com_b, const ripp_g1j* com_t,
+                              const ripp_gt* com_gt, const ripp_g1j* com_ped, const ripp_g1j* com_ip,
+                              const ripp_g1j* base_a, const ripp_fr* base_b, int32_t* accept);
 /* UNSTABLE diagnostics, not part of the drop-in boundary (it serves tools/tpc_first_tier_ab.py and may change or go): the milliseconds the commitments and inner products of every round (key lengths n, n / 2, .. 2) of the LAST first-tier prover of this process
  * took to reach the host; returns the number of rounds.  RIPP_TPC_CROSS_MIN (environment) moves the key length from which a round's two Pedersen
- * commitments run as one crossed pass of the batched MSM pipeline instead of two single MSMs; unmeasured so far, hence off by default. */
+ * commitments run as one crossed pass of the batched MSM pipeline instead of two single MSMs; profiles/tpc_first_tier_ab.txt has the per-round table, the default is still off. */
 int32_t ripp_tpc_round_ms(double* out, size_t cap);
 
 /* ---- wire format: ark-serialize 0.4 images of the proof structs, host only ---------------------

@@ -15,7 +15,7 @@ from ._lib import lib, last_error, RippStats, AggregateProof, VerifierSRSStruct,
 
 __all__ = ["InnerProductError", "DeviceError", "Vec", "PairingInnerProduct", "MultiexponentiationInnerProductG1",
            "MultiexponentiationInnerProductG2", "ScalarInnerProduct", "AFGHOCommitmentG1", "AFGHOCommitmentG2", "PedersenCommitmentG1",
-           "PedersenCommitmentG2", "SIPP", "SippJob", "GIPA_TIPP", "SRS", "TIPA_TIPP", "TIPAWithSSM", "aggregate_proofs", "aggregate_proofs_sharded", "gipa_tipp_prove_sharded", "verify_aggregate_proof", "AggregateProof", "ser_tipa_tipp_proof", "de_tipa_tipp_proof", "ser_tipa_ssm_proof", "de_tipa_ssm_proof", "ser_g1_compressed", "ser_g2_compressed", "product_of_pairings", "product_of_pairings_with_coeffs",
+           "PedersenCommitmentG2", "SIPP", "SippJob", "GIPA_TIPP", "GIPA_MEXP", "SRS", "TIPA_TIPP", "TIPAWithSSM", "aggregate_proofs", "aggregate_proofs_sharded", "gipa_tipp_prove_sharded", "verify_aggregate_proof", "AggregateProof", "ser_tipa_tipp_proof", "de_tipa_tipp_proof", "ser_tipa_ssm_proof", "de_tipa_ssm_proof", "ser_g1_compressed", "ser_g2_compressed", "product_of_pairings", "product_of_pairings_with_coeffs",
            "normalize_batch_g1", "normalize_batch_g2", "fold_g1_affine", "fold_g2_affine", "fold_g1", "fold_g2",
            "scale_g1_affine", "synth_g1", "synth_g2", "synth_fr", "init", "device_count", "final_exponentiation",
            "ser_gt", "ser_g1", "ser_g2", "ser_fr", "sipp_seed_digest", "gt_mul", "statement_hash_times", "configure", "config_default", "config_get", "release_scratch", "device_bytes"]
@@ -501,6 +501,61 @@ class GIPA_TIPP:
         ba = np.ascontiguousarray(r_base[0], dtype=np.uint64).reshape(18); bb = np.ascontiguousarray(r_base[1], dtype=np.uint64).reshape(36)
         acc = ctypes.c_int32(0)
         _check(lib().ripp_gipa_tipp_verify(_p(ck_a), _p(ck_b), ctypes.c_size_t(n), _p(com), _p(steps), ctypes.c_size_t(len(steps) // 6), _p(ba), _p(bb), ctypes.byref(acc)))
+        return bool(acc.value)
+
+
+class GIPA_MEXP:
+    """GIPA<MultiexponentiationInnerProduct<G1>, AFGHOCommitmentG1, PedersenCommitment<G1>, IdentityCommitment<G1>, Blake2b>
+    (ip_proofs/src/gipa.rs:499-530, benches/benches/gipa.rs case 2): the fused, device-resident form of
+    ripp_amd.gipa.GIPA(MultiexpIPG1, AFGHOCommitmentG1, PedersenCommitmentG1, IdentityCommitment(G1)).  The dict layout is that module's -- proof =
+    {r_commitment_steps (reversed): [((gt, ped, [ip]), (gt, ped, [ip]))], r_base: (m_a[0], m_b[0])}, aux = {r_transcript (reversed), ck_base: (ck_a[0], ck_b[0])} --
+    so a proof of either prover can be handed to either verifier."""
+
+    @staticmethod
+    def _affine(keys, cols):
+        """keys as the C ABI takes them (affine); the projective layout of the trait-level API is normalised first"""
+        k = np.ascontiguousarray(keys, dtype=np.uint64)
+        if k.ndim == 2 and k.shape[1] == cols * 3 // 2:
+            k = normalize_batch_g2(k) if cols == 24 else normalize_batch_g1(k)
+        return _c(k, cols)
+
+    @staticmethod
+    def prove_with_aux(m_a, m_b, ck_a, ck_b):
+        """m_a (n,18) projective G1, m_b (n,4) Fr, ck_a affine (n,24) or projective (n,36) G2, ck_b affine (n,12) or projective (n,18) G1; n a power of two >= 2.
+        -> (proof, aux, extra): extra has the steps and the transcript in ROUND order and the call's ripp_stats."""
+        m_a, m_b, ck_a, ck_b = _c(m_a, 18), _c(m_b, 4), GIPA_MEXP._affine(ck_a, 24), GIPA_MEXP._affine(ck_b, 12)
+        n = len(m_a)
+        assert len(m_b) == len(ck_a) == len(ck_b) == n
+        rounds = max(n.bit_length() - 1, 1)
+        gt = np.zeros((rounds * 2, 72), dtype=np.uint64); ped = np.zeros((rounds * 2, 18), dtype=np.uint64); ip = np.zeros((rounds * 2, 18), dtype=np.uint64)
+        tr = np.zeros((rounds, 4), dtype=np.uint64)
+        ba = np.zeros(18, dtype=np.uint64); bb = np.zeros(4, dtype=np.uint64); ka = np.zeros(36, dtype=np.uint64); kb = np.zeros(18, dtype=np.uint64)
+        st = RippStats()
+        _check(lib().ripp_gipa_mexp_prove(_p(m_a), _p(m_b), _p(ck_a), _p(ck_b), ctypes.c_size_t(n), _p(gt), _p(ped), _p(ip), _p(tr), _p(ba), _p(bb), _p(ka), _p(kb), ctypes.byref(st)))
+        steps = [((gt[2 * k], ped[2 * k], [ip[2 * k]]), (gt[2 * k + 1], ped[2 * k + 1], [ip[2 * k + 1]])) for k in range(rounds)]
+        proof = {"r_commitment_steps": steps[::-1], "r_base": (ba, bb)}
+        aux = {"r_transcript": tr[::-1].copy(), "ck_base": (ka, kb)}
+        return proof, aux, {"round_order_com_gt": gt, "round_order_com_ped": ped, "round_order_com_ip": ip, "round_order_transcript": tr, "stats": st.as_dict()}
+
+    @staticmethod
+    def verify(ck, com, proof):
+        """GIPA::verify (gipa.rs:135-160).  ck = (ck_a, ck_b[, ck_t]) affine keys, com = (com_a in GT, com_b in G1, com_t: the inner product or [it]),
+        proof as returned by prove_with_aux or by ripp_amd.gipa.GIPA.prove_with_aux."""
+        ck_a, ck_b = GIPA_MEXP._affine(ck[0], 24), GIPA_MEXP._affine(ck[1], 12); n = len(ck_a)
+        assert len(ck_b) == n
+        steps = proof["r_commitment_steps"][::-1]                      # ROUND order
+        if len(steps) != max(n.bit_length() - 1, 0) or n & (n - 1):
+            return False
+        com_t = com[2][0] if isinstance(com[2], (list, tuple)) else com[2]
+        ca, cb, ct = _a(com[0], 72), _a(com[1], 18), _a(com_t, 18)
+        r = max(len(steps), 1)
+        gt = np.zeros((r * 2, 72), dtype=np.uint64); ped = np.zeros((r * 2, 18), dtype=np.uint64); ip = np.zeros((r * 2, 18), dtype=np.uint64)
+        for k, sides in enumerate(steps):
+            for j, side in enumerate(sides):
+                gt[2 * k + j], ped[2 * k + j], ip[2 * k + j] = _a(side[0], 72), _a(side[1], 18), _a(side[2][0], 18)
+        ba, bb = _a(proof["r_base"][0], 18), _a(proof["r_base"][1], 4)
+        acc = ctypes.c_int32(0)
+        _check(lib().ripp_gipa_mexp_verify(_p(ck_a), _p(ck_b), ctypes.c_size_t(n), _p(ca), _p(cb), _p(ct), _p(gt), _p(ped), _p(ip), _p(ba), _p(bb), ctypes.byref(acc)))
         return bool(acc.value)
 
 

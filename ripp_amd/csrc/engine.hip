@@ -41,6 +41,7 @@
 #include "fq_msm.hpp"
 #include "msm_batch.hpp"
 #include "tpc.hpp"
+#include "gipa_mexp.hpp"
 #include "vm_fold2.hpp"
 #include "host_fs.hpp"
 #include "wire.hpp"
@@ -345,11 +346,17 @@ struct Engine {
     struct Sizes { size_t vm_lines_max, vm_fold_max, vm_tree_max, gls_split_max, msm_vm_merge_max, fold_tab_min, fq_min, lp_fq_min, vm_joint_max, vm_scale_max, tail_pipe_max, ml_fq_min, fq_min_g1, msm_lds_sort_min, msm_chunk_min; } defaults{};
     MsmTune msm_tune;
     // First-tier rounds of the transparent polynomial commitment (tpc_api.inc): key vectors of at least this length commit with the crossed two-row
-    // batch pass, shorter ones with two single MSMs on two streams.  UNMEASURED so far: whether and from which length the crossed form wins is what
-    // tools/tpc_first_tier_ab.py tabulates (its output belongs in profiles/tpc_first_tier_ab.txt, which does not exist yet), so no round takes the crossed
-    // form by default.  RIPP_TPC_CROSS_MIN overrides the bound per call (2: every round crossed).
+    // batch pass, shorter ones with two single MSMs on two streams.  tools/tpc_first_tier_ab.py tabulates both forms per round length in
+    // profiles/tpc_first_tier_ab.txt (crossed ahead at key length 4096, behind at 2048, level below); the bound has not been moved on that one table yet, so no
+    // round takes the crossed form by default.  RIPP_TPC_CROSS_MIN overrides the bound per call (2: every round crossed).
     static constexpr size_t TPC_CROSS_MIN = ~(size_t)0;
     size_t tpc_cross_min = TPC_CROSS_MIN;
+    // Rounds of the GIPA prover with a committed scalar vector (gipa_mexp_api.inc): vectors of at least this length run the round's four G1 MSMs as ONE
+    // four-row pass of the batched pipeline (gipa_mexp.hpp), shorter ones as four single MSMs on two side streams.  profiles/gipa_mexp_ab.txt
+    // (tools/gipa_mexp_ab.py): with every round in one pass the whole proof's median is below the four-MSM form's minimum at every measured n = 2^4 .. 2^16
+    // (0.85 - 0.93 of it); 16 is the shortest measured length.  RIPP_GIPA_MEXP_BATCH_MIN overrides the bound per call (2: every round in one pass).
+    static constexpr size_t GIPA_MEXP_BATCH_MIN = 16;
+    size_t gipa_mexp_batch_min = GIPA_MEXP_BATCH_MIN;
     // the hash-window look-ahead plan and a few whole-call choices (ripp_config: look_eighths, ranks_per_device, look_static, quiet_waits, agg_sequential, scale_no_fq)
     double cal_ms_per_pair = 0, cal_hash_bytes_per_ms = 0;        // look_plan's rates as measured by the last large proof of this process (0: not yet)
     int look_eighths = -1; double ranks_per_device = 1.0; bool look_static = false, quiet_waits_cfg = false, agg_sequential = false, scale_no_fq = false;
@@ -396,6 +403,7 @@ struct Engine {
           env_u32("RIPP_COMM_TIMEOUT_MS", comm_timeout_ms); env_u32("RIPP_PLAN_DERATE_PCT", plan_derate_pct); env_u32("RIPP_N_DEVICES", n_devices_cfg);
           virtual_devices = false; if (const char* s = std::getenv("RIPP_VIRTUAL_DEVICES")) { n_devices_cfg = (uint32_t)std::strtoul(s, nullptr, 10); virtual_devices = true; } }
         tpc_cross_min = TPC_CROSS_MIN; env_sz("RIPP_TPC_CROSS_MIN", tpc_cross_min);      // crossed two-row commitments of the first-tier rounds from this key length on (A/B)
+        gipa_mexp_batch_min = GIPA_MEXP_BATCH_MIN; env_sz("RIPP_GIPA_MEXP_BATCH_MIN", gipa_mexp_batch_min);      // four-row pass of a committed-scalar GIPA round from this vector length on (A/B)
         env_on("RIPP_NO_MSM_BATCH", sw.no_msm_batch);  // batched shared-base MSMs as a loop of single MSMs over the rows (A/B; the form the legacy MSM switches select too)
         env_on("RIPP_NO_PREBUILD", sw.no_prebuild);    // in-round G2 fold tables after the challenge (fold_g2_table), not in the host phase before it (job_prebuild_g2_tables)
         env_on("RIPP_NO_FUSE", sw.no_fuse);            // rounds 0 and 1 always fold one after the other (no three-quarter tables, no job_fold_fused)
@@ -628,12 +636,23 @@ struct Engine {
     }
     // cross_h != 0: the crossed form of tpc.hpp -- rows = 2, cols = 2 cross_h, scalars = ONE vector m of cols elements; row 0 = (m[h:], 0), row 1 = (0, m[:h]).
     // The legacy switches have no crossed form: the caller asks msm_batch_legacy() first and runs two msm_launch calls instead.
+    // quad_len != 0: the four-row form of gipa_mexp.hpp -- rows = 4, cols = 2 quad_len bases (ck_b | m_a), scalars = ONE vector m_b of quad_len elements.  Like the
+    // crossed form it needs the batched pipeline and one chunk: the caller asks msm_batch_legacy() and msm_quad_fits() first.
     bool msm_batch_legacy() const { return sw.no_msm_batch || sw.no_msm_glv || sw.no_fq || sw.no_vm; }
-    int32_t msm_batch_dev(const G1A* bases, const QAff<Fp>* ext, const Fr* scalars, size_t rows, size_t cols, size_t stride, G1J* out_dev, uint32_t cross_h = 0) {
+    bool msm_quad_fits(size_t len) {
+        const MsmPlan p = msm_plan_batch(2 * len, 2, 4, msm_tune);
+        const size_t max_slots = (size_t)p.n / p.ch + std::min<size_t>(p.nb, p.n) + 1;
+        if (4 * (size_t)p.nwin > 65535 || 4 * (size_t)p.nwin * max_slots >= ((size_t)1 << 32)) return false;
+        MsmScratch& ms = msm_batch;
+        size_t held = 0; for (DevBuf* b : {&ms.digits, &ms.hist, &ms.offs, &ms.cursor, &ms.slotoffs, &ms.spw, &ms.sorted, &ms.slots, &ms.buckets, &ms.seg, &ms.seg2, &ms.flags}) held += b->cap;
+        return mem_fits(msm_batch_bytes(p, 4), held);
+    }
+    int32_t msm_batch_dev(const G1A* bases, const QAff<Fp>* ext, const Fr* scalars, size_t rows, size_t cols, size_t stride, G1J* out_dev, uint32_t cross_h = 0, uint32_t quad_len = 0) {
         msm_batch_chunks = 0;
         if (rows == 0) return RIPP_OK;
         hipStream_t st = stream; int32_t rc;
         if (cross_h && (rows != 2 || cols != 2 * (size_t)cross_h || msm_batch_legacy())) { set_err("msm_batch_dev: the crossed form takes two rows over 2 h bases on the batched pipeline"); return RIPP_ERR_ARG; }
+        if (quad_len && (cross_h || rows != 4 || cols != 2 * (size_t)quad_len || quad_len < 2 || msm_batch_legacy())) { set_err("msm_batch_dev: the four-row form takes four rows over 2 len bases on the batched pipeline"); return RIPP_ERR_ARG; }
         if (cols == 0) { const G1J inf = jac_inf<Fp>(); std::vector<G1J> z(rows, inf); HIPCHK(hipMemcpyAsync(out_dev, z.data(), rows * sizeof(G1J), hipMemcpyHostToDevice, st)); return sync(); }
         if (msm_batch_legacy()) {
             for (size_t r = 0; r < rows; ++r) {
@@ -671,6 +690,9 @@ struct Engine {
             if (cross_h) {
                 if (Rc != 2) { set_err("msm_batch_dev: the crossed form does not fit one chunk"); return RIPP_ERR_DEVICE; }
                 hipLaunchKernelGGL(k_tpc_digits_cross, dim3(nblk(cols, 256), 2), dim3(256), 0, st, scalars, cross_h, p, ms.digits.as<uint16_t>());
+            } else if (quad_len) {
+                if (Rc != 4) { set_err("msm_batch_dev: the four-row form does not fit one chunk"); return RIPP_ERR_DEVICE; }
+                hipLaunchKernelGGL(k_gipa_mexp_digits, dim3(nblk(quad_len, 256)), dim3(256), 0, st, scalars, quad_len, p, ms.digits.as<uint16_t>());
             } else
             hipLaunchKernelGGL(k_msm_digits_batch, dim3(nblk(cols, 256), (unsigned)Rc), dim3(256), 0, st, scalars + r0 * stride, (uint32_t)cols, stride, p, ms.digits.as<uint16_t>());
             hipLaunchKernelGGL(k_msm_hist_lds, dim3(nblk(n, tile), pb.nwin), dim3(MSM_SORT_BLOCK), 0, st, ms.digits.as<uint16_t>(), pb, tile, ms.hist.as<uint32_t>());
@@ -2886,6 +2908,8 @@ API int32_t ripp_sipp_challenge(uint8_t seed[32], const ripp_gt* z_l, const ripp
 #include "poly_commit_api.inc"      // KZG / bivariate / univariate polynomial commitments on a resident SRS handle, the batched shared-base MSM
 
 #include "tpc_api.inc"       // transparent polynomial commitments on a resident key handle, the two GIPAWithSSM tier arguments
+
+#include "gipa_mexp_api.inc" // GIPA with a committed scalar vector (MIPP): fused prover and verifier, the round's four G1 MSMs as one batched pass
 
 #include "wire_api.inc"      // CanonicalSerialize / CanonicalDeserialize images of the proof structs (zcash layout on BLS12-381, generic SWFlags layout on BLS12-377: wire.hpp)
 
