@@ -533,6 +533,43 @@ int32_t ripp_gipa_mexp_verify(const ripp_g2a* ck_a, const ripp_g1a* ck_b, size_t
                               const ripp_gt* com_a, const ripp_g1j* com_b, const ripp_g1j* com_t,
                               const ripp_gt* com_gt, const ripp_g1j* com_ped, const ripp_g1j* com_ip,
                               const ripp_g1j* base_a, const ripp_fr* base_b, int32_t* accept);
+/* TIPA over the same argument: TIPA<MultiexponentiationInnerProduct<G1>, AFGHOCommitmentG1, PedersenCommitment<G1>, IdentityCommitment<G1>, Blake2b>
+ * (tipa/mod.rs:473-497, benches/benches/tipa.rs case 2).  TIPA::prove_with_srs_shift (mod.rs:176-231): the rounds of ripp_gipa_mexp_prove, then the KZG
+ * openings of both final keys as in ripp_tipa_tipp_prove.  Keys are affine host slices; the caller passes the shifted ck_a when r_shift != 1.
+ * srs must hold 2n-1 powers (RIPP_ERR_ARG).  Steps and transcript in ROUND order, laid out as for ripp_gipa_mexp_prove.  Argument errors are reported
+ * before the device is looked for and nothing is allocated on a failure path.  Single device. */
+int32_t ripp_tipa_mexp_prove(const ripp_srs* srs, const ripp_g1j* m_a, const ripp_fr* m_b, const ripp_g2a* ck_a, const ripp_g1a* ck_b, size_t n,
+                             const ripp_fr* r_shift, ripp_gt* com_gt, ripp_g1j* com_ped, ripp_g1j* com_ip, ripp_fr* transcript,
+                             ripp_g1j* base_a, ripp_fr* base_b, ripp_g2j* final_ck_a, ripp_g1j* final_ck_b,
+                             ripp_g2j* opening_a, ripp_g1j* opening_b, ripp_fr* kzg_challenge, ripp_stats* stats);
+/* TIPA::verify_with_srs_shift (mod.rs:233-301): replay, both KZG checks (mod.rs:274-289), base check e(base_a, final_ck_a) == com_a,
+ * base_b * final_ck_b == com_b, base_b * base_a == com_t (mod.rs:291-298).  Takes no keys: logarithmic time.  A step that is no GT element gives
+ * accept = 0 with RIPP_OK. */
+int32_t ripp_tipa_mexp_verify(const ripp_verifier_srs* v_srs, const ripp_gt* com_a, const ripp_g1j* com_b, const ripp_g1j* com_t,
+                              const ripp_gt* com_gt, const ripp_g1j* com_ped, const ripp_g1j* com_ip, size_t rounds,
+                              const ripp_g1j* base_a, const ripp_fr* base_b, const ripp_g2j* final_ck_a, const ripp_g1j* final_ck_b,
+                              const ripp_g2j* opening_a, const ripp_g1j* opening_b, const ripp_fr* r_shift, int32_t* accept);
+/* TIPA for scalar products: TIPA<ScalarInnerProduct, PedersenCommitment<G2>, PedersenCommitment<G1>, IdentityCommitment<Fr>, Blake2b> (tipa/mod.rs:499-526).
+ * m_a, m_b in Fr, ck_a in G2 and ck_b in G1 (Pedersen keys, affine host slices; the shifted ck_a when r_shift != 1).  n a power of two, 2 <= n <= 2^24
+ * (RIPP_ERR_POW2); srs must hold 2n-1 powers (RIPP_ERR_ARG).  Steps in ROUND order (gipa.rs:207-291):
+ *   com_g2[r][2] = (com_1.0, com_2.0)   Pedersen commitments of the m_a halves under ck_a
+ *   com_g1[r][2] = (com_1.1, com_2.1)   Pedersen commitments of the m_b halves under ck_b
+ *   com_fr[r][2] = (com_1.2[0], com_2.2[0])   the inner products
+ * Argument errors are reported before the device is looked for and nothing is allocated on a failure path.  Single device.  ripp_stats: miller_products_ms
+ * holds the round's commitments and inner products (there is no Miller loop), fold_ms, host_ms, total_ms.
+ * RIPP_TIPA_SCALAR_CROSS_MIN (environment) moves the key length from which a round's two G2 commitments run as ONE crossed pass of the batched MSM
+ * pipeline in its G2 form (and the two G1 commitments as one crossed pass of the G1 form) instead of two single MSMs each; profiles/tipa_scalar_ab.txt
+ * has the measurement behind the default. */
+int32_t ripp_tipa_scalar_prove(const ripp_srs* srs, const ripp_fr* m_a, const ripp_fr* m_b, const ripp_g2a* ck_a, const ripp_g1a* ck_b, size_t n,
+                               const ripp_fr* r_shift, ripp_g2j* com_g2 /* [r][2] */, ripp_g1j* com_g1 /* [r][2] */, ripp_fr* com_fr /* [r][2] */,
+                               ripp_fr* transcript /* [r] */, ripp_fr* base_a, ripp_fr* base_b, ripp_g2j* final_ck_a, ripp_g1j* final_ck_b,
+                               ripp_g2j* opening_a, ripp_g1j* opening_b, ripp_fr* kzg_challenge, ripp_stats* stats);
+/* TIPA::verify_with_srs_shift (mod.rs:233-301) for it: replay in G2 / G1 / Fr, both KZG checks, base check base_a * final_ck_a == com_a,
+ * base_b * final_ck_b == com_b, base_a * base_b == com_t.  com = (com_a in G2, com_b in G1, com_t in Fr).  Takes no keys: logarithmic time. */
+int32_t ripp_tipa_scalar_verify(const ripp_verifier_srs* v_srs, const ripp_g2j* com_a, const ripp_g1j* com_b, const ripp_fr* com_t,
+                                const ripp_g2j* com_g2, const ripp_g1j* com_g1, const ripp_fr* com_fr, size_t rounds,
+                                const ripp_fr* base_a, const ripp_fr* base_b, const ripp_g2j* final_ck_a, const ripp_g1j* final_ck_b,
+                                const ripp_g2j* opening_a, const ripp_g1j* opening_b, const ripp_fr* r_shift, int32_t* accept);
 /* UNSTABLE diagnostics, not part of the drop-in boundary (it serves tools/tpc_first_tier_ab.py and may change or go): the milliseconds the commitments and inner products of every round (key lengths n, n / 2, .. 2) of the LAST first-tier prover of this process
  * took to reach the host; returns the number of rounds.  RIPP_TPC_CROSS_MIN (environment) moves the key length from which a round's two Pedersen
  * commitments run as one crossed pass of the batched MSM pipeline instead of two single MSMs; profiles/tpc_first_tier_ab.txt has the per-round table, the default is still off. */

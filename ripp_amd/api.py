@@ -15,7 +15,7 @@ from ._lib import lib, last_error, RippStats, AggregateProof, VerifierSRSStruct,
 
 __all__ = ["InnerProductError", "DeviceError", "Vec", "PairingInnerProduct", "MultiexponentiationInnerProductG1",
            "MultiexponentiationInnerProductG2", "ScalarInnerProduct", "AFGHOCommitmentG1", "AFGHOCommitmentG2", "PedersenCommitmentG1",
-           "PedersenCommitmentG2", "SIPP", "SippJob", "GIPA_TIPP", "GIPA_MEXP", "SRS", "TIPA_TIPP", "TIPAWithSSM", "aggregate_proofs", "aggregate_proofs_sharded", "gipa_tipp_prove_sharded", "verify_aggregate_proof", "AggregateProof", "ser_tipa_tipp_proof", "de_tipa_tipp_proof", "ser_tipa_ssm_proof", "de_tipa_ssm_proof", "ser_g1_compressed", "ser_g2_compressed", "product_of_pairings", "product_of_pairings_with_coeffs",
+           "PedersenCommitmentG2", "SIPP", "SippJob", "GIPA_TIPP", "GIPA_MEXP", "SRS", "TIPA_TIPP", "TIPA_MEXP", "TIPA_SCALAR", "TIPAWithSSM", "aggregate_proofs", "aggregate_proofs_sharded", "gipa_tipp_prove_sharded", "verify_aggregate_proof", "AggregateProof", "ser_tipa_tipp_proof", "de_tipa_tipp_proof", "ser_tipa_ssm_proof", "de_tipa_ssm_proof", "ser_g1_compressed", "ser_g2_compressed", "product_of_pairings", "product_of_pairings_with_coeffs",
            "normalize_batch_g1", "normalize_batch_g2", "fold_g1_affine", "fold_g2_affine", "fold_g1", "fold_g2",
            "scale_g1_affine", "synth_g1", "synth_g2", "synth_fr", "init", "device_count", "final_exponentiation",
            "ser_gt", "ser_g1", "ser_g2", "ser_fr", "sipp_seed_digest", "gt_mul", "statement_hash_times", "configure", "config_default", "config_get", "release_scratch", "device_bytes"]
@@ -658,6 +658,94 @@ class TIPA_TIPP:
     @staticmethod
     def verify(v_srs, com, proof):
         return TIPA_TIPP.verify_with_srs_shift(v_srs, com, proof, FR_ONE)
+
+
+class TIPA_MEXP:
+    """TIPA<MultiexponentiationInnerProduct<G1>, AFGHOCommitmentG1, PedersenCommitment<G1>, IdentityCommitment<G1,Fr>, Blake2b>
+    (tipa/mod.rs:473-497, benches/benches/tipa.rs case 2): the committed-scalar MIPP argument with a logarithmic verifier."""
+
+    @staticmethod
+    def prove_with_srs_shift(srs, values, ck, r_shift):
+        """tipa/mod.rs:176-231.  values = (m_a G1 (n,18), m_b Fr (n,4)), ck = (ck_a G2, ck_b G1), affine or projective; ck_a already shifted when r_shift != 1.
+        Returns a dict with the GIPA steps in ROUND order."""
+        m_a, m_b, ck_a, ck_b = _c(values[0], 18), _c(values[1], 4), GIPA_MEXP._affine(ck[0], 24), GIPA_MEXP._affine(ck[1], 12)
+        n = len(m_a); assert len(m_b) == len(ck_a) == len(ck_b) == n
+        rounds = max(n.bit_length() - 1, 1)
+        o = dict(com_gt=np.zeros((rounds * 2, 72), dtype=np.uint64), com_ped=np.zeros((rounds * 2, 18), dtype=np.uint64), com_ip=np.zeros((rounds * 2, 18), dtype=np.uint64),
+                 tr=np.zeros((rounds, 4), dtype=np.uint64), base_a=np.zeros(18, dtype=np.uint64), base_b=np.zeros(4, dtype=np.uint64),
+                 final_ck_a=np.zeros(36, dtype=np.uint64), final_ck_b=np.zeros(18, dtype=np.uint64),
+                 opening_a=np.zeros(36, dtype=np.uint64), opening_b=np.zeros(18, dtype=np.uint64), kzg_c=np.zeros(4, dtype=np.uint64))
+        st = RippStats()
+        _check(lib().ripp_tipa_mexp_prove(srs._h, _p(m_a), _p(m_b), _p(ck_a), _p(ck_b), ctypes.c_size_t(n), _p(_a(r_shift, 4)), _p(o["com_gt"]), _p(o["com_ped"]), _p(o["com_ip"]),
+                                          _p(o["tr"]), _p(o["base_a"]), _p(o["base_b"]), _p(o["final_ck_a"]), _p(o["final_ck_b"]), _p(o["opening_a"]), _p(o["opening_b"]),
+                                          _p(o["kzg_c"]), ctypes.byref(st)))
+        o["stats"] = st.as_dict(); return o
+
+    @staticmethod
+    def prove(srs, values, ck):
+        """tipa/mod.rs:168-174: r_shift = 1."""
+        return TIPA_MEXP.prove_with_srs_shift(srs, values, ck, FR_ONE)
+
+    @staticmethod
+    def verify_with_srs_shift(v_srs, com, proof, r_shift):
+        """tipa/mod.rs:242-301.  com = (com_a GT, com_b G1 projective, com_t G1 projective); proof: dict of prove_with_srs_shift."""
+        vs = _vsrs(v_srs)
+        gt = np.ascontiguousarray(proof["com_gt"], dtype=np.uint64).reshape(-1, 72); ped = np.ascontiguousarray(proof["com_ped"], dtype=np.uint64).reshape(-1, 18)
+        ip = np.ascontiguousarray(proof["com_ip"], dtype=np.uint64).reshape(-1, 18)
+        assert len(ped) == len(gt) and len(ip) == len(gt)
+        acc = ctypes.c_int32(0)
+        _check(lib().ripp_tipa_mexp_verify(ctypes.byref(vs), _p(_a(com[0], 72)), _p(_a(com[1], 18)), _p(_a(com[2], 18)), _p(gt), _p(ped), _p(ip), ctypes.c_size_t(len(gt) // 2),
+                                           _p(_a(proof["base_a"], 18)), _p(_a(proof["base_b"], 4)), _p(_a(proof["final_ck_a"], 36)), _p(_a(proof["final_ck_b"], 18)),
+                                           _p(_a(proof["opening_a"], 36)), _p(_a(proof["opening_b"], 18)), _p(_a(r_shift, 4)), ctypes.byref(acc)))
+        return bool(acc.value)
+
+    @staticmethod
+    def verify(v_srs, com, proof):
+        return TIPA_MEXP.verify_with_srs_shift(v_srs, com, proof, FR_ONE)
+
+
+class TIPA_SCALAR:
+    """TIPA<ScalarInnerProduct, PedersenCommitment<G2>, PedersenCommitment<G1>, IdentityCommitment<Fr,Fr>, Blake2b> (tipa/mod.rs:499-526):
+    the inner product of two committed scalar vectors."""
+
+    @staticmethod
+    def prove_with_srs_shift(srs, values, ck, r_shift):
+        """tipa/mod.rs:176-231.  values = (m_a, m_b) Fr (n,4), ck = (ck_a G2, ck_b G1), affine or projective; ck_a already shifted when r_shift != 1.
+        Returns a dict with the GIPA steps in ROUND order: com_g2 / com_g1 / com_fr [r][2] = (com_1.k, com_2.k)."""
+        m_a, m_b, ck_a, ck_b = _c(values[0], 4), _c(values[1], 4), GIPA_MEXP._affine(ck[0], 24), GIPA_MEXP._affine(ck[1], 12)
+        n = len(m_a); assert len(m_b) == len(ck_a) == len(ck_b) == n
+        rounds = max(n.bit_length() - 1, 1)
+        o = dict(com_g2=np.zeros((rounds * 2, 36), dtype=np.uint64), com_g1=np.zeros((rounds * 2, 18), dtype=np.uint64), com_fr=np.zeros((rounds * 2, 4), dtype=np.uint64),
+                 tr=np.zeros((rounds, 4), dtype=np.uint64), base_a=np.zeros(4, dtype=np.uint64), base_b=np.zeros(4, dtype=np.uint64),
+                 final_ck_a=np.zeros(36, dtype=np.uint64), final_ck_b=np.zeros(18, dtype=np.uint64),
+                 opening_a=np.zeros(36, dtype=np.uint64), opening_b=np.zeros(18, dtype=np.uint64), kzg_c=np.zeros(4, dtype=np.uint64))
+        st = RippStats()
+        _check(lib().ripp_tipa_scalar_prove(srs._h, _p(m_a), _p(m_b), _p(ck_a), _p(ck_b), ctypes.c_size_t(n), _p(_a(r_shift, 4)), _p(o["com_g2"]), _p(o["com_g1"]), _p(o["com_fr"]),
+                                            _p(o["tr"]), _p(o["base_a"]), _p(o["base_b"]), _p(o["final_ck_a"]), _p(o["final_ck_b"]), _p(o["opening_a"]), _p(o["opening_b"]),
+                                            _p(o["kzg_c"]), ctypes.byref(st)))
+        o["stats"] = st.as_dict(); return o
+
+    @staticmethod
+    def prove(srs, values, ck):
+        """tipa/mod.rs:168-174: r_shift = 1."""
+        return TIPA_SCALAR.prove_with_srs_shift(srs, values, ck, FR_ONE)
+
+    @staticmethod
+    def verify_with_srs_shift(v_srs, com, proof, r_shift):
+        """tipa/mod.rs:242-301.  com = (com_a G2 projective, com_b G1 projective, com_t Fr); proof: dict of prove_with_srs_shift."""
+        vs = _vsrs(v_srs)
+        g2 = np.ascontiguousarray(proof["com_g2"], dtype=np.uint64).reshape(-1, 36); g1 = np.ascontiguousarray(proof["com_g1"], dtype=np.uint64).reshape(-1, 18)
+        fr = np.ascontiguousarray(proof["com_fr"], dtype=np.uint64).reshape(-1, 4)
+        assert len(g1) == len(g2) and len(fr) == len(g2)
+        acc = ctypes.c_int32(0)
+        _check(lib().ripp_tipa_scalar_verify(ctypes.byref(vs), _p(_a(com[0], 36)), _p(_a(com[1], 18)), _p(_a(com[2], 4)), _p(g2), _p(g1), _p(fr), ctypes.c_size_t(len(g2) // 2),
+                                             _p(_a(proof["base_a"], 4)), _p(_a(proof["base_b"], 4)), _p(_a(proof["final_ck_a"], 36)), _p(_a(proof["final_ck_b"], 18)),
+                                             _p(_a(proof["opening_a"], 36)), _p(_a(proof["opening_b"], 18)), _p(_a(r_shift, 4)), ctypes.byref(acc)))
+        return bool(acc.value)
+
+    @staticmethod
+    def verify(v_srs, com, proof):
+        return TIPA_SCALAR.verify_with_srs_shift(v_srs, com, proof, FR_ONE)
 
 
 class TIPAWithSSM:

@@ -42,6 +42,7 @@
 #include "msm_batch.hpp"
 #include "tpc.hpp"
 #include "gipa_mexp.hpp"
+#include "tipa_scalar.hpp"
 #include "vm_fold2.hpp"
 #include "host_fs.hpp"
 #include "wire.hpp"
@@ -357,6 +358,13 @@ struct Engine {
     // (0.85 - 0.93 of it); 16 is the shortest measured length.  RIPP_GIPA_MEXP_BATCH_MIN overrides the bound per call (2: every round in one pass).
     static constexpr size_t GIPA_MEXP_BATCH_MIN = 16;
     size_t gipa_mexp_batch_min = GIPA_MEXP_BATCH_MIN;
+    // Rounds of the TIPA prover for scalar products (tipa_scalar_api.inc): key vectors of at least this length commit with ONE crossed two-row pass of the batched
+    // pipeline in G2 (tipa_scalar.hpp) followed by one in G1, shorter ones (and every round under the legacy MSM switches) with two single MSMs per group on two
+    // side streams.  tools/tipa_scalar_ab.py tabulates both forms in profiles/tipa_scalar_ab.txt (whole proofs, n = 2^4 .. 2^16): the crossed form is within a few
+    // per cent of the two-MSM form either way and NOT ahead at the longest measured size, so by the rule in that file's header no round takes it by default.
+    // RIPP_TIPA_SCALAR_CROSS_MIN overrides the bound per call (2: every round crossed).
+    static constexpr size_t TIPA_SCALAR_CROSS_MIN = ~(size_t)0;
+    size_t tipa_scalar_cross_min = TIPA_SCALAR_CROSS_MIN;
     // the hash-window look-ahead plan and a few whole-call choices (ripp_config: look_eighths, ranks_per_device, look_static, quiet_waits, agg_sequential, scale_no_fq)
     double cal_ms_per_pair = 0, cal_hash_bytes_per_ms = 0;        // look_plan's rates as measured by the last large proof of this process (0: not yet)
     int look_eighths = -1; double ranks_per_device = 1.0; bool look_static = false, quiet_waits_cfg = false, agg_sequential = false, scale_no_fq = false;
@@ -403,6 +411,7 @@ struct Engine {
           env_u32("RIPP_COMM_TIMEOUT_MS", comm_timeout_ms); env_u32("RIPP_PLAN_DERATE_PCT", plan_derate_pct); env_u32("RIPP_N_DEVICES", n_devices_cfg);
           virtual_devices = false; if (const char* s = std::getenv("RIPP_VIRTUAL_DEVICES")) { n_devices_cfg = (uint32_t)std::strtoul(s, nullptr, 10); virtual_devices = true; } }
         tpc_cross_min = TPC_CROSS_MIN; env_sz("RIPP_TPC_CROSS_MIN", tpc_cross_min);      // crossed two-row commitments of the first-tier rounds from this key length on (A/B)
+        tipa_scalar_cross_min = TIPA_SCALAR_CROSS_MIN; env_sz("RIPP_TIPA_SCALAR_CROSS_MIN", tipa_scalar_cross_min);      // crossed G2 / G1 commitments of a scalar-product TIPA round from this key length on (A/B)
         gipa_mexp_batch_min = GIPA_MEXP_BATCH_MIN; env_sz("RIPP_GIPA_MEXP_BATCH_MIN", gipa_mexp_batch_min);      // four-row pass of a committed-scalar GIPA round from this vector length on (A/B)
         env_on("RIPP_NO_MSM_BATCH", sw.no_msm_batch);  // batched shared-base MSMs as a loop of single MSMs over the rows (A/B; the form the legacy MSM switches select too)
         env_on("RIPP_NO_PREBUILD", sw.no_prebuild);    // in-round G2 fold tables after the challenge (fold_g2_table), not in the host phase before it (job_prebuild_g2_tables)
@@ -624,57 +633,65 @@ struct Engine {
         return RIPP_OK;
     }
 
-    // ---- batched shared-base G1 MSM (msm_batch.hpp): out_dev[r] = sum_{i < cols} scalars[r * stride + i] * bases[i], r < rows -----------------------
-    // bases, scalars, out_dev: device memory.  ext (optional): the extended base array of EXACTLY the first `cols` bases (k_msm_extend_q with split 2), kept
+    // ---- batched shared-base MSM (msm_batch.hpp): out_dev[r] = sum_{i < cols} scalars[r * stride + i] * bases[i], r < rows -------------------------
+    // One pipeline for both groups: F = Fp is the G1 form (terms split two ways over the GLV endomorphism), F = Fp2 the G2 form (four ways over psi, as
+    // msm_launch<Fp2>); every stage after the digit pass is the same template.  The G2 form exists for the crossed two-row pass only (tipa_scalar.hpp).
+    // bases, scalars, out_dev: device memory.  ext (optional): the extended base array of EXACTLY the first `cols` bases (k_msm_extend_q with the group's split), kept
     // resident by a ripp_pc_srs; without it the array is built once per call -- never per row.  Enqueued on `stream`; the caller synchronises.
     // Rows are processed in chunks when the scratch of the whole batch (digits and sorted indices grow with rows x windows x terms) does not fit
     // ripp_config.mem_cap_bytes / free memory; every chunk runs the same plan, so a chunked run gives the same points.
     // Legacy switches (no_msm_glv, no_fq, no_vm) and RIPP_NO_MSM_BATCH: the per-row loop of msm_launch, which honours them.
-    static size_t msm_batch_bytes(const MsmPlan& p, size_t R) {
+    template <class F> static constexpr int msm_batch_split() { return std::is_same<F, Fp>::value ? 2 : 4; }
+    template <class F> static size_t msm_batch_bytes(const MsmPlan& p, size_t R) {
         const size_t W = R * (size_t)p.nwin, n = p.n, max_slots = n / p.ch + std::min<size_t>(p.nb, n) + 1, nseg = (p.nb + p.seg - 1) / p.seg;
-        return W * (n * 6 + (size_t)p.nb * 16 + 4 + max_slots * (sizeof(G1J) + 1) + ((size_t)p.nb + nseg + (nseg + MSM_SEG_FAN - 1) / MSM_SEG_FAN) * sizeof(G1J)) + 16;
+        return W * (n * 6 + (size_t)p.nb * 16 + 4 + max_slots * (sizeof(Jac<F>) + 1) + ((size_t)p.nb + nseg + (nseg + MSM_SEG_FAN - 1) / MSM_SEG_FAN) * sizeof(Jac<F>)) + 16;
     }
-    // cross_h != 0: the crossed form of tpc.hpp -- rows = 2, cols = 2 cross_h, scalars = ONE vector m of cols elements; row 0 = (m[h:], 0), row 1 = (0, m[:h]).
-    // The legacy switches have no crossed form: the caller asks msm_batch_legacy() first and runs two msm_launch calls instead.
+    // cross_h != 0: the crossed form of tpc.hpp (G1) / tipa_scalar.hpp (G2) -- rows = 2, cols = 2 cross_h, scalars = ONE vector m of cols elements; row 0 = (m[h:], 0),
+    // row 1 = (0, m[:h]).  The legacy switches have no crossed form: the caller asks msm_batch_legacy() first and runs two msm_launch calls instead.
     // quad_len != 0: the four-row form of gipa_mexp.hpp -- rows = 4, cols = 2 quad_len bases (ck_b | m_a), scalars = ONE vector m_b of quad_len elements.  Like the
-    // crossed form it needs the batched pipeline and one chunk: the caller asks msm_batch_legacy() and msm_quad_fits() first.
+    // crossed form it needs the batched pipeline and one chunk: the caller asks msm_batch_legacy() and msm_quad_fits() / msm_rows_fit() first.
     bool msm_batch_legacy() const { return sw.no_msm_batch || sw.no_msm_glv || sw.no_fq || sw.no_vm; }
-    bool msm_quad_fits(size_t len) {
-        const MsmPlan p = msm_plan_batch(2 * len, 2, 4, msm_tune);
+    // `rows` rows over `cols` bases run as ONE chunk: grid.y, the 32-bit slot index of the fix-up kernels and the memory budget
+    template <class F> bool msm_rows_fit(size_t cols, size_t rows) {
+        const MsmPlan p = msm_plan_batch(cols, msm_batch_split<F>(), rows, msm_tune);
         const size_t max_slots = (size_t)p.n / p.ch + std::min<size_t>(p.nb, p.n) + 1;
-        if (4 * (size_t)p.nwin > 65535 || 4 * (size_t)p.nwin * max_slots >= ((size_t)1 << 32)) return false;
+        if (rows * (size_t)p.nwin > 65535 || rows * (size_t)p.nwin * max_slots >= ((size_t)1 << 32)) return false;
         MsmScratch& ms = msm_batch;
         size_t held = 0; for (DevBuf* b : {&ms.digits, &ms.hist, &ms.offs, &ms.cursor, &ms.slotoffs, &ms.spw, &ms.sorted, &ms.slots, &ms.buckets, &ms.seg, &ms.seg2, &ms.flags}) held += b->cap;
-        return mem_fits(msm_batch_bytes(p, 4), held);
+        return mem_fits(msm_batch_bytes<F>(p, rows), held);
     }
-    int32_t msm_batch_dev(const G1A* bases, const QAff<Fp>* ext, const Fr* scalars, size_t rows, size_t cols, size_t stride, G1J* out_dev, uint32_t cross_h = 0, uint32_t quad_len = 0) {
+    bool msm_quad_fits(size_t len) { return msm_rows_fit<Fp>(2 * len, 4); }
+    template <class F> int32_t msm_batch_dev(const Affine<F>* bases, const QAff<F>* ext, const Fr* scalars, size_t rows, size_t cols, size_t stride, Jac<F>* out_dev, uint32_t cross_h = 0, uint32_t quad_len = 0) {
+        constexpr bool g1 = std::is_same<F, Fp>::value;
+        constexpr int split = msm_batch_split<F>();
         msm_batch_chunks = 0;
         if (rows == 0) return RIPP_OK;
         hipStream_t st = stream; int32_t rc;
+        if (!g1 && !cross_h) { set_err("msm_batch_dev: the G2 pipeline has the crossed form only"); return RIPP_ERR_ARG; }
         if (cross_h && (rows != 2 || cols != 2 * (size_t)cross_h || msm_batch_legacy())) { set_err("msm_batch_dev: the crossed form takes two rows over 2 h bases on the batched pipeline"); return RIPP_ERR_ARG; }
         if (quad_len && (cross_h || rows != 4 || cols != 2 * (size_t)quad_len || quad_len < 2 || msm_batch_legacy())) { set_err("msm_batch_dev: the four-row form takes four rows over 2 len bases on the batched pipeline"); return RIPP_ERR_ARG; }
-        if (cols == 0) { const G1J inf = jac_inf<Fp>(); std::vector<G1J> z(rows, inf); HIPCHK(hipMemcpyAsync(out_dev, z.data(), rows * sizeof(G1J), hipMemcpyHostToDevice, st)); return sync(); }
+        if (cols == 0) { const Jac<F> inf = jac_inf<F>(); std::vector<Jac<F>> z(rows, inf); HIPCHK(hipMemcpyAsync(out_dev, z.data(), rows * sizeof(Jac<F>), hipMemcpyHostToDevice, st)); return sync(); }
         if (msm_batch_legacy()) {
             for (size_t r = 0; r < rows; ++r) {
-                if ((rc = msm_launch<Fp>(msm_scratch[0], st, bases, scalars + r * stride, cols))) return rc;
-                HIPCHK(hipMemcpyAsync(out_dev + r, msm_scratch[0].out.p, sizeof(G1J), hipMemcpyDeviceToDevice, st));
+                if ((rc = msm_launch<F>(msm_scratch[0], st, bases, scalars + r * stride, cols))) return rc;
+                HIPCHK(hipMemcpyAsync(out_dev + r, msm_scratch[0].out.p, sizeof(Jac<F>), hipMemcpyDeviceToDevice, st));
             }
             return RIPP_OK;
         }
         MsmScratch& ms = msm_batch;
-        const MsmPlan p = msm_plan_batch(cols, 2, rows, msm_tune);
+        const MsmPlan p = msm_plan_batch(cols, split, rows, msm_tune);
         const size_t n = p.n, max_slots = n / p.ch + std::min<size_t>(p.nb, n) + 1;
         // rows per chunk: grid.y and the 32-bit slot index of the fix-up kernels bound it first, then the memory budget (halving; one row always runs)
         size_t R = std::min<size_t>(rows, std::min<size_t>(65535 / (size_t)p.nwin, (((size_t)1 << 32) - 1) / ((size_t)p.nwin * max_slots)));
         R = std::max<size_t>(R, 1);
         size_t held = 0; for (DevBuf* b : {&ms.digits, &ms.hist, &ms.offs, &ms.cursor, &ms.slotoffs, &ms.spw, &ms.sorted, &ms.slots, &ms.buckets, &ms.seg, &ms.seg2, &ms.flags}) held += b->cap;
-        while (R > 1 && !mem_fits(msm_batch_bytes(p, R), held)) R = (R + 1) / 2;
+        while (R > 1 && !mem_fits(msm_batch_bytes<F>(p, R), held)) R = (R + 1) / 2;
         if (!ext) {
-            if ((rc = ms.ext.reserve(n * sizeof(G1A)))) return rc;
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_msm_extend_q<Fp>), dim3(nblk(cols, 256), 2), dim3(256), 0, st, bases, (uint32_t)cols, 2, ms.ext.as<QAff<Fp>>());
-            ext = ms.ext.as<QAff<Fp>>();
+            if ((rc = ms.ext.reserve(n * sizeof(Affine<F>)))) return rc;
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_msm_extend_q<F>), dim3(nblk(cols, 256), split), dim3(256), 0, st, bases, (uint32_t)cols, split, ms.ext.as<QAff<F>>());
+            ext = ms.ext.as<QAff<F>>();
         }
-        const size_t vm_lds = 4 * VM_EPW * VmCurve<Fp>::SLOTS * sizeof(VmSlot);
+        const size_t vm_lds = 4 * VM_EPW * VmCurve<F>::SLOTS * sizeof(VmSlot);
         for (size_t r0 = 0; r0 < rows; r0 += R, ++msm_batch_chunks) {
             const size_t Rc = std::min(R, rows - r0);
             MsmPlan pb = p; pb.nwin = (int)(Rc * (size_t)p.nwin);                      // the chunk's virtual windows
@@ -682,44 +699,47 @@ struct Engine {
             uint32_t nseg = (p.nb + p.seg - 1) / p.seg;
             if ((rc = ms.digits.reserve(W * n * sizeof(uint16_t))) || (rc = ms.hist.reserve(nwb * 4)) || (rc = ms.offs.reserve(nwb * 4)) ||
                 (rc = ms.cursor.reserve(nwb * 4)) || (rc = ms.slotoffs.reserve(nwb * 4)) || (rc = ms.spw.reserve(W * 4)) ||
-                (rc = ms.sorted.reserve(W * n * 4)) || (rc = ms.slots.reserve(W * max_slots * sizeof(G1J))) ||
-                (rc = ms.buckets.reserve(nwb * sizeof(G1J))) || (rc = ms.seg.reserve(W * nseg * sizeof(G1J))) ||
-                (rc = ms.seg2.reserve(W * ((nseg + MSM_SEG_FAN - 1) / MSM_SEG_FAN) * sizeof(G1J))) || (rc = ms.flags.reserve(W * max_slots + 16))) return rc;
+                (rc = ms.sorted.reserve(W * n * 4)) || (rc = ms.slots.reserve(W * max_slots * sizeof(Jac<F>))) ||
+                (rc = ms.buckets.reserve(nwb * sizeof(Jac<F>))) || (rc = ms.seg.reserve(W * nseg * sizeof(Jac<F>))) ||
+                (rc = ms.seg2.reserve(W * ((nseg + MSM_SEG_FAN - 1) / MSM_SEG_FAN) * sizeof(Jac<F>))) || (rc = ms.flags.reserve(W * max_slots + 16))) return rc;
             HIPCHK(hipMemsetAsync(ms.hist.p, 0, nwb * 4, st));
             const uint32_t tile = msm_sort_tile(pb);
             if (cross_h) {
                 if (Rc != 2) { set_err("msm_batch_dev: the crossed form does not fit one chunk"); return RIPP_ERR_DEVICE; }
-                hipLaunchKernelGGL(k_tpc_digits_cross, dim3(nblk(cols, 256), 2), dim3(256), 0, st, scalars, cross_h, p, ms.digits.as<uint16_t>());
-            } else if (quad_len) {
-                if (Rc != 4) { set_err("msm_batch_dev: the four-row form does not fit one chunk"); return RIPP_ERR_DEVICE; }
-                hipLaunchKernelGGL(k_gipa_mexp_digits, dim3(nblk(quad_len, 256)), dim3(256), 0, st, scalars, quad_len, p, ms.digits.as<uint16_t>());
-            } else
-            hipLaunchKernelGGL(k_msm_digits_batch, dim3(nblk(cols, 256), (unsigned)Rc), dim3(256), 0, st, scalars + r0 * stride, (uint32_t)cols, stride, p, ms.digits.as<uint16_t>());
+                if constexpr (g1) hipLaunchKernelGGL(k_tpc_digits_cross, dim3(nblk(cols, 256), 2), dim3(256), 0, st, scalars, cross_h, p, ms.digits.as<uint16_t>());
+                else hipLaunchKernelGGL(k_tipa_scalar_digits_cross_g2, dim3(nblk(cols, 256), 2), dim3(256), 0, st, scalars, cross_h, p, ms.digits.as<uint16_t>());
+            } else if constexpr (g1) {
+                if (quad_len) {
+                    if (Rc != 4) { set_err("msm_batch_dev: the four-row form does not fit one chunk"); return RIPP_ERR_DEVICE; }
+                    hipLaunchKernelGGL(k_gipa_mexp_digits, dim3(nblk(quad_len, 256)), dim3(256), 0, st, scalars, quad_len, p, ms.digits.as<uint16_t>());
+                } else
+                hipLaunchKernelGGL(k_msm_digits_batch, dim3(nblk(cols, 256), (unsigned)Rc), dim3(256), 0, st, scalars + r0 * stride, (uint32_t)cols, stride, p, ms.digits.as<uint16_t>());
+            }
             hipLaunchKernelGGL(k_msm_hist_lds, dim3(nblk(n, tile), pb.nwin), dim3(MSM_SORT_BLOCK), 0, st, ms.digits.as<uint16_t>(), pb, tile, ms.hist.as<uint32_t>());
             hipLaunchKernelGGL(k_msm_scan, dim3(pb.nwin), dim3(1024), 0, st, ms.hist.as<uint32_t>(), pb, ms.offs.as<uint32_t>(), ms.cursor.as<uint32_t>(), ms.slotoffs.as<uint32_t>(), ms.spw.as<uint32_t>());
             hipLaunchKernelGGL(k_msm_scatter_lds, dim3(nblk(n, tile), pb.nwin), dim3(MSM_SORT_BLOCK), 0, st, ms.digits.as<uint16_t>(), pb, tile, ms.cursor.as<uint32_t>(), ms.sorted.as<uint32_t>());
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_msm_slot_sum_q<Fp>), dim3(nblk(max_slots, 64), pb.nwin), dim3(64), 0, st, ext, pb, ms.hist.as<uint32_t>(), ms.offs.as<uint32_t>(),
-                               ms.slotoffs.as<uint32_t>(), ms.spw.as<uint32_t>(), ms.sorted.as<uint32_t>(), ms.slots.as<G1J>(), (uint32_t)max_slots, true, ms.flags.as<uint8_t>());
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_msm_slot_sum_fix_vm<Fp>), dim3(FIX_GRID), dim3(64), VM_EPW * VmCurve<Fp>::SLOTS * sizeof(VmSlot), st, bases, pb, ms.hist.as<uint32_t>(), ms.offs.as<uint32_t>(),
-                               ms.slotoffs.as<uint32_t>(), ms.spw.as<uint32_t>(), ms.sorted.as<uint32_t>(), ms.slots.as<G1J>(), (uint32_t)max_slots, ms.flags.as<uint8_t>(), (uint32_t*)nullptr);
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_msm_slot_sum_q<F>), dim3(nblk(max_slots, 64), pb.nwin), dim3(64), 0, st, ext, pb, ms.hist.as<uint32_t>(), ms.offs.as<uint32_t>(),
+                               ms.slotoffs.as<uint32_t>(), ms.spw.as<uint32_t>(), ms.sorted.as<uint32_t>(), ms.slots.as<Jac<F>>(), (uint32_t)max_slots, true, ms.flags.as<uint8_t>());
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_msm_slot_sum_fix_vm<F>), dim3(FIX_GRID), dim3(64), VM_EPW * VmCurve<F>::SLOTS * sizeof(VmSlot), st, bases, pb, ms.hist.as<uint32_t>(), ms.offs.as<uint32_t>(),
+                               ms.slotoffs.as<uint32_t>(), ms.spw.as<uint32_t>(), ms.sorted.as<uint32_t>(), ms.slots.as<Jac<F>>(), (uint32_t)max_slots, ms.flags.as<uint8_t>(), (uint32_t*)nullptr);
             uint32_t passes = 0;
             for (uint32_t gs = 1; passes < (uint32_t)MSM_GROUP_PASSES && n / p.ch + 1 > (size_t)p.gmin * gs; gs *= MSM_SLOT_GROUP, ++passes)
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_msm_slot_group<Fp>), dim3(nblk(max_slots, 64), pb.nwin), dim3(64), 0, st, pb, ms.hist.as<uint32_t>(),
-                                   ms.slotoffs.as<uint32_t>(), ms.spw.as<uint32_t>(), ms.slots.as<G1J>(), (uint32_t)max_slots, gs, true);
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_msm_slot_group<F>), dim3(nblk(max_slots, 64), pb.nwin), dim3(64), 0, st, pb, ms.hist.as<uint32_t>(),
+                                   ms.slotoffs.as<uint32_t>(), ms.spw.as<uint32_t>(), ms.slots.as<Jac<F>>(), (uint32_t)max_slots, gs, true);
             if (nwb <= msm_vm_merge_max)
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_msm_vm_merge<Fp>), dim3(nblk(p.nb, 4 * VM_EPW), pb.nwin), dim3(256), vm_lds, st, pb, ms.hist.as<uint32_t>(), ms.slotoffs.as<uint32_t>(),
-                                   ms.slots.as<G1J>(), (uint32_t)max_slots, ms.buckets.as<G1J>(), passes);
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_msm_vm_merge<F>), dim3(nblk(p.nb, 4 * VM_EPW), pb.nwin), dim3(256), vm_lds, st, pb, ms.hist.as<uint32_t>(), ms.slotoffs.as<uint32_t>(),
+                                   ms.slots.as<Jac<F>>(), (uint32_t)max_slots, ms.buckets.as<Jac<F>>(), passes);
             else
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_msm_bucket_merge<Fp>), dim3(nblk(p.nb, 64), pb.nwin), dim3(64), 0, st, pb, ms.hist.as<uint32_t>(), ms.slotoffs.as<uint32_t>(),
-                                   ms.slots.as<G1J>(), (uint32_t)max_slots, ms.buckets.as<G1J>(), passes, true);
-            G1J* cur = ms.seg.as<G1J>(); G1J* nxt = ms.seg2.as<G1J>();
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_msm_vm_segments<Fp>), dim3(nblk(nseg, 4 * VM_EPW), pb.nwin), dim3(256), vm_lds, st, pb, ms.buckets.as<G1J>(), cur, nseg);
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_msm_bucket_merge<F>), dim3(nblk(p.nb, 64), pb.nwin), dim3(64), 0, st, pb, ms.hist.as<uint32_t>(), ms.slotoffs.as<uint32_t>(),
+                                   ms.slots.as<Jac<F>>(), (uint32_t)max_slots, ms.buckets.as<Jac<F>>(), passes, true);
+            Jac<F>* cur = ms.seg.as<Jac<F>>(); Jac<F>* nxt = ms.seg2.as<Jac<F>>();
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_msm_vm_segments<F>), dim3(nblk(nseg, 4 * VM_EPW), pb.nwin), dim3(256), vm_lds, st, pb, ms.buckets.as<Jac<F>>(), cur, nseg);
             while (nseg > 1) {
                 const uint32_t nout = (nseg + MSM_SEG_FAN - 1) / MSM_SEG_FAN;
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_msm_vm_reduce<Fp>), dim3(nblk(nout, 4 * VM_EPW), pb.nwin), dim3(256), vm_lds, st, cur, nseg, nxt, nout);
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_msm_vm_reduce<F>), dim3(nblk(nout, 4 * VM_EPW), pb.nwin), dim3(256), vm_lds, st, cur, nseg, nxt, nout);
                 std::swap(cur, nxt); nseg = nout;
             }
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_msm_finish_vm_batch<Fp>), dim3(nblk(Rc, VM_EPW)), dim3(64), VM_EPW * VmCurve<Fp>::SLOTS * sizeof(VmSlot), st, p, (uint32_t)Rc, cur, out_dev + r0);
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_msm_finish_vm_batch<F>), dim3(nblk(Rc, VM_EPW)), dim3(64), VM_EPW * VmCurve<F>::SLOTS * sizeof(VmSlot), st, p, (uint32_t)Rc, cur, out_dev + r0);
             HIPCHK(hipGetLastError());
         }
         return RIPP_OK;
@@ -2910,6 +2930,10 @@ API int32_t ripp_sipp_challenge(uint8_t seed[32], const ripp_gt* z_l, const ripp
 #include "tpc_api.inc"       // transparent polynomial commitments on a resident key handle, the two GIPAWithSSM tier arguments
 
 #include "gipa_mexp_api.inc" // GIPA with a committed scalar vector (MIPP): fused prover and verifier, the round's four G1 MSMs as one batched pass
+
+#include "tipa_mexp_api.inc" // TIPA over the same argument: the rounds of gipa_mexp_api.inc followed by the KZG openings of both final keys, logarithmic verifier
+
+#include "tipa_scalar_api.inc" // TIPA for scalar products (Pedersen keys in G2 and G1): the round's commitments as crossed passes of the batched MSM pipeline in both groups
 
 #include "wire_api.inc"      // CanonicalSerialize / CanonicalDeserialize images of the proof structs (zcash layout on BLS12-381, generic SWFlags layout on BLS12-377: wire.hpp)
 

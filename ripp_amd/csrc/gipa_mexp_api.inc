@@ -41,7 +41,7 @@ static int32_t gipa_mexp_rounds(Engine* e, MexpVecs& v, size_t n, ripp_gt* com_g
         const bool batch = !e->msm_batch_legacy() && len >= e->gipa_mexp_batch_min && e->msm_quad_fits(len);
         const double tp = now_ms();
         if (batch) {            // one digit pass and one sort for the four MSMs, in front of the pairing products on the engine's stream
-            if ((rc = e->msm_batch_dev(KB, nullptr, S, 4, 2 * len, 0, out, 0, (uint32_t)len))) return rc;
+            if ((rc = e->msm_batch_dev<Fp>(KB, nullptr, S, 4, 2 * len, 0, out, 0, (uint32_t)len))) return rc;
         } else {                // two MSMs after one another on each side stream, beside the pairing products; each scratch is reused in stream order
             struct { hipStream_t st; int ms; const G1A* b; const Fr* s; } q[4] = {{e->stream2, 0, KB + h, S}, {e->stream3, 1, A + h, S}, {e->stream2, 0, KB, S + h}, {e->stream3, 1, A, S + h}};
             for (int k = 0; k < 4; ++k) {

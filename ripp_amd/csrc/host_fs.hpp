@@ -321,6 +321,28 @@ inline Fr gipa_mexp_challenge(const Fr* prev, const Fp12 gt[2], const G1A ped[2]
     }
 }
 
+// GIPA challenge with PedersenCommitment<G2> on the left, PedersenCommitment<G1> on the right and IdentityCommitment<Fr> for the inner product,
+// TIPA<ScalarInnerProduct, PedersenCommitment<G2>, PedersenCommitment<G1>, IdentityCommitment<Fr>> (gipa.rs:235-258 instantiated as in tipa/mod.rs:499-526):
+// per side  G2 (192) || G1 (96) || u64 1 || Fr (32).
+inline Fr gipa_scalar_challenge(const Fr* prev, const G2A g2[2], const G1A g1[2], const Fr ip[2], Fr& c_inv) {
+    for (uint64_t nonce = 0;; ++nonce) {
+        uint8_t buf[8 + 32 + 2 * (192 + 96 + 8 + 32)], *p = buf;
+        for (int i = 0; i < 8; ++i) *p++ = (uint8_t)(nonce >> (56 - 8 * i));
+        ser_fr(prev ? *prev : Fr::zero(), p); p += 32;
+        for (int k = 0; k < 2; ++k) {
+            ser_g2(g2[k], p); p += 192;
+            ser_g1(g1[k], p); p += 96;
+            const uint64_t one = 1; std::memcpy(p, &one, 8); p += 8;
+            ser_fr(ip[k], p); p += 32;
+        }
+        uint8_t dig[64]; Blake2b h; h.update(buf, (size_t)(p - buf)); h.finish(dig);
+        uint64_t hi = 0, lo = 0;
+        for (int i = 0; i < 8; ++i) { hi = (hi << 8) | dig[i]; lo = (lo << 8) | dig[8 + i]; }
+        const Fr c128 = fr_from_u128(lo, hi);
+        if (!c128.is_zero()) { c_inv = c128; return inv(c128); }
+    }
+}
+
 // GIPA challenge of the first tier of the transparent polynomial commitment, GIPAWithSSM<ScalarInnerProduct, PedersenCommitment<G1>,
 // IdentityCommitment<Fr>> (transparent.rs:43-48; gipa.rs:235-258): per side  G1 (96) || Fr::zero() (32) || u64 1 || Fr (32).
 inline Fr gipa_scalar_ssm_challenge(const Fr* prev, const G1A g1[2], const Fr ip[2], Fr& c_inv) {

@@ -37,7 +37,7 @@ static int32_t two_tier_commit(Engine* e, const TwoTier& k, const Fr* dcoef, siz
     int32_t rc;
     if ((rc = e->pc_out.reserve(k.nx * sizeof(G1J))) || (rc = e->pc_aff.reserve(k.nx * sizeof(G1A)))) return rc;
     HIPCHK(hipMemsetAsync(e->pc_out.p, 0, k.nx * sizeof(G1J), e->stream));            // Z = 0: the identity
-    if ((rc = e->msm_batch_dev(k.bases, cols == k.ny ? k.ext : nullptr, dcoef, rows, cols, stride, e->pc_out.as<G1J>()))) return rc;
+    if ((rc = e->msm_batch_dev<Fp>(k.bases, cols == k.ny ? k.ext : nullptr, dcoef, rows, cols, stride, e->pc_out.as<G1J>()))) return rc;
     HIPCHK(hipMemcpyAsync(y_coms, e->pc_out.p, k.nx * sizeof(G1J), hipMemcpyDeviceToHost, e->stream));
     if ((rc = e->normalize_dev<Fp>(e->pc_out.as<G1J>(), k.nx, e->pc_aff.as<G1A>()))) return rc;
     if ((rc = e->sync())) return rc;
@@ -212,7 +212,7 @@ API int32_t ripp_msm_g1_batch_a(const ripp_g1a* bases, size_t n, const ripp_fr* 
     LOCK; ENGINE;
     int32_t rc; G1A* db; Fr* ds;
     if ((rc = upload<G1A>(e, e->affG1, bases, cols, &db)) || (rc = pc_upload_matrix(e, scalars, rows, cols, stride, &ds)) || (rc = e->pc_out.reserve(rows * sizeof(G1J)))) return rc;
-    if ((rc = e->msm_batch_dev(db, nullptr, ds, rows, cols, cols, e->pc_out.as<G1J>()))) return rc;
+    if ((rc = e->msm_batch_dev<Fp>(db, nullptr, ds, rows, cols, cols, e->pc_out.as<G1J>()))) return rc;
     HIPCHK(hipMemcpyAsync(out, e->pc_out.p, rows * sizeof(G1J), hipMemcpyDeviceToHost, e->stream));
     return e->sync();
 }

@@ -18,9 +18,9 @@ struct VecBufCache { std::vector<DevBuf> bufs; bool full = false;
     // the auxiliary engine's) streams, and the next call adopts the same buffers, possibly on other streams.  ~10 us on an idle device, once per call.
     void park(std::initializer_list<DevBuf*> l) { (void)hipDeviceSynchronize(); if (full) { for (DevBuf* b : l) b->release(); return; } bufs.resize(l.size()); size_t i = 0; for (DevBuf* b : l) { bufs[i].release(); std::swap(*b, bufs[i++]); } full = true; }
     void release() { for (DevBuf& b : bufs) b.release(); full = false; } };
-static VecBufCache g_tipp_cache, g_ssm_cache, g_mexp_cache;      // (g_mexp_cache: the vector set of gipa_mexp_api.inc)
+static VecBufCache g_tipp_cache, g_ssm_cache, g_mexp_cache, g_scal_cache;      // (g_mexp_cache: the vector set of gipa_mexp_api.inc and tipa_mexp_api.inc, g_scal_cache: that of tipa_scalar_api.inc)
 static FoldPre g_tpc_pre;                  // second fold base of the first-tier key folds (tpc_api.inc)
-static void vec_caches_release() { g_tipp_cache.release(); g_ssm_cache.release(); g_mexp_cache.release(); g_tpc_pre.release(); }
+static void vec_caches_release() { g_tipp_cache.release(); g_ssm_cache.release(); g_mexp_cache.release(); g_scal_cache.release(); g_tpc_pre.release(); }
 template <class F> static int32_t fold_precompute(Engine* e, hipStream_t st, const Affine<F>* hi, size_t half, FoldPre& fp) {
     fp.ready = false;
     if (half == 0 || half > e->vm_fold_max || e->sw.no_vm || e->sw.no_precompute) return RIPP_OK;

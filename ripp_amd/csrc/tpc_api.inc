@@ -109,7 +109,7 @@ static int32_t tpc_scalar_rounds(Engine* e, size_t n, const QAff<Fp>* ext0, ripp
         const double tp = now_ms();
         G1J cm[2];
         if (cross) {         // com_1.0 = <ck[:h], m[h:]>, com_2.0 = <ck[h:], m[:h]> as rows 0 and 1 over the whole key vector   gipa.rs:209-231
-            if ((rc = e->msm_batch_dev(K, round == 0 ? ext0 : nullptr, M, 2, len, 0, e->tpc_out.as<G1J>(), (uint32_t)h))) return rc;
+            if ((rc = e->msm_batch_dev<Fp>(K, round == 0 ? ext0 : nullptr, M, 2, len, 0, e->tpc_out.as<G1J>(), (uint32_t)h))) return rc;
             HIPCHK(hipMemcpyAsync(cm, e->tpc_out.p, sizeof cm, hipMemcpyDeviceToHost, e->stream));
         } else {
             if ((rc = e->msm_launch<Fp>(e->msm_scratch[0], e->stream2, K, M + h, h)) || (rc = e->msm_launch<Fp>(e->msm_scratch[1], e->stream3, K + h, M, h))) return rc;

@@ -247,6 +247,10 @@ extern "C" {
     pub fn ripp_gipa_ssm_mexp_verify(ck: *const RippG2A, n: usize, com_a: *const RippGt, com_t: *const RippG1J, scalar_b: *const RippFr, com_gt: *const RippGt, com_g1: *const RippG1J, base_a: *const RippG1J, base_b: *const RippFr, accept: *mut i32) -> i32;
     pub fn ripp_gipa_mexp_prove(m_a: *const RippG1J, m_b: *const RippFr, ck_a: *const RippG2A, ck_b: *const RippG1A, n: usize, com_gt: *mut RippGt, com_ped: *mut RippG1J, com_ip: *mut RippG1J, transcript: *mut RippFr, base_a: *mut RippG1J, base_b: *mut RippFr, ck_base_a: *mut RippG2J, ck_base_b: *mut RippG1J, stats: *mut RippStats) -> i32;
     pub fn ripp_gipa_mexp_verify(ck_a: *const RippG2A, ck_b: *const RippG1A, n: usize, com_a: *const RippGt, com_b: *const RippG1J, com_t: *const RippG1J, com_gt: *const RippGt, com_ped: *const RippG1J, com_ip: *const RippG1J, base_a: *const RippG1J, base_b: *const RippFr, accept: *mut i32) -> i32;
+    pub fn ripp_tipa_mexp_prove(srs: *const RippSrs, m_a: *const RippG1J, m_b: *const RippFr, ck_a: *const RippG2A, ck_b: *const RippG1A, n: usize, r_shift: *const RippFr, com_gt: *mut RippGt, com_ped: *mut RippG1J, com_ip: *mut RippG1J, transcript: *mut RippFr, base_a: *mut RippG1J, base_b: *mut RippFr, final_ck_a: *mut RippG2J, final_ck_b: *mut RippG1J, opening_a: *mut RippG2J, opening_b: *mut RippG1J, kzg_challenge: *mut RippFr, stats: *mut RippStats) -> i32;
+    pub fn ripp_tipa_mexp_verify(v_srs: *const RippVerifierSrs, com_a: *const RippGt, com_b: *const RippG1J, com_t: *const RippG1J, com_gt: *const RippGt, com_ped: *const RippG1J, com_ip: *const RippG1J, rounds: usize, base_a: *const RippG1J, base_b: *const RippFr, final_ck_a: *const RippG2J, final_ck_b: *const RippG1J, opening_a: *const RippG2J, opening_b: *const RippG1J, r_shift: *const RippFr, accept: *mut i32) -> i32;
+    pub fn ripp_tipa_scalar_prove(srs: *const RippSrs, m_a: *const RippFr, m_b: *const RippFr, ck_a: *const RippG2A, ck_b: *const RippG1A, n: usize, r_shift: *const RippFr, com_g2: *mut RippG2J, com_g1: *mut RippG1J, com_fr: *mut RippFr, transcript: *mut RippFr, base_a: *mut RippFr, base_b: *mut RippFr, final_ck_a: *mut RippG2J, final_ck_b: *mut RippG1J, opening_a: *mut RippG2J, opening_b: *mut RippG1J, kzg_challenge: *mut RippFr, stats: *mut RippStats) -> i32;
+    pub fn ripp_tipa_scalar_verify(v_srs: *const RippVerifierSrs, com_a: *const RippG2J, com_b: *const RippG1J, com_t: *const RippFr, com_g2: *const RippG2J, com_g1: *const RippG1J, com_fr: *const RippFr, rounds: usize, base_a: *const RippFr, base_b: *const RippFr, final_ck_a: *const RippG2J, final_ck_b: *const RippG1J, opening_a: *const RippG2J, opening_b: *const RippG1J, r_shift: *const RippFr, accept: *mut i32) -> i32;
     pub fn ripp_tpc_round_ms(out: *mut f64, cap: usize) -> i32;
     pub fn ripp_ser_tipa_tipp_proof(com_steps: *const RippGt, rounds: usize, base_a: *const RippG1J, base_b: *const RippG2J, final_ck_a: *const RippG2J, final_ck_b: *const RippG1J, opening_a: *const RippG2J, opening_b: *const RippG1J, compress: i32, out: *mut u8, cap: usize) -> usize;
     pub fn ripp_de_tipa_tipp_proof(in_: *const u8, len: usize, compress: i32, with_tipa: i32, max_rounds: usize, rounds: *mut usize, com_steps: *mut RippGt, base_a: *mut RippG1J, base_b: *mut RippG2J, final_ck_a: *mut RippG2J, final_ck_b: *mut RippG1J, opening_a: *mut RippG2J, opening_b: *mut RippG1J) -> i32;

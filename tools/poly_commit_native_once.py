@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
 """One native univariate polynomial commitment at a given degree -- setup, a warm-up commit and open, then `--reps` timed commits and opens -- for
 profiling (`rocprofv3 --kernel-trace --stats -- python tools/poly_commit_native_once.py`) and as the shortest end-to-end example of
-ripp_amd/poly_commit/native.py.  The evaluation the library returns is checked against Horner, the proof by the native verifier.
+ripp_amd/poly_commit/native.py.  The evaluation the library returns is checked against Horner, the proof by the native verifier.  The last line is
+one SHA-256 over every output (commitment, y_polynomial_comms, proof members, value), group elements normalised first: equal between two builds of
+the library (RIPP_HIP_LIB selects another one) exactly when they compute the same values.
 
   python tools/poly_commit_native_once.py [--degree 1048575] [--reps 1]"""
-import argparse, os, sys, time
+import argparse, hashlib, os, statistics, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
@@ -30,8 +32,15 @@ def main():
         acc = (acc * zi + int.from_bytes(raw[32 * i:32 * i + 32], "little") * rinv) % P.R_MOD
     assert np.array_equal(val, P.frs([acc])[0]), "evaluation differs from Horner"
     assert U.verify(srs.verifier_key(), args.degree, com, z, val, proof)
-    print(f"degree {args.degree} (x_degree, y_degree) = {srs.degrees()}: setup {t_setup * 1e3:.1f} ms, commit {min(tc) * 1e3:.2f} ms, open {min(to) * 1e3:.2f} ms (min of {args.reps}); "
+    print(f"degree {args.degree} (x_degree, y_degree) = {srs.degrees()}: setup {t_setup * 1e3:.1f} ms, commit {min(tc) * 1e3:.2f} ms, open {min(to) * 1e3:.2f} ms (min of {args.reps}; medians {statistics.median(tc) * 1e3:.3f} / {statistics.median(to) * 1e3:.3f} ms); "
           f"evaluation = Horner, proof accepted; device bytes {R.device_bytes()}")
+    ip = proof["ip_proof"]
+    g1 = np.concatenate([np.asarray(coms).reshape(-1, 18), ip["com_g1"], ip["base_a"][None], proof["y_eval_comm"][None], proof["kzg_proof"][None]])
+    g2 = np.stack([ip["final_ck_a"], ip["opening_a"]])
+    h = hashlib.sha256()
+    for part in (np.asarray(com), R.normalize_batch_g1(g1), R.normalize_batch_g2(g2), ip["com_gt"], ip["tr"], ip["base_b"], ip["kzg_c"], np.asarray(val)):
+        h.update(np.ascontiguousarray(part, dtype=np.uint64).tobytes())
+    print(f"outputs sha256 {h.hexdigest()} ({len(g1)} G1, {len(g2)} G2 points normalised)")
     srs.close()
 
 
