@@ -11,11 +11,7 @@ extern "C++" {
 struct MexpVecs {
     DevBuf X, X2, S, S2, KA, KA2, jacA, jacK, jac2, qt2, out;
     FoldPre pA, pKB, pKA;                   // second fold bases of the small rounds
-#define RIPP_MEXP_BUFS {&X, &X2, &S, &S2, &KA, &KA2, &jacA, &jacK, &jac2, &qt2, &out, &pA.pow_h, &pA.parts, &pKB.pow_h, &pKB.parts, &pKA.pow_h, &pKA.parts}
-    MexpVecs() { g_mexp_cache.adopt(RIPP_MEXP_BUFS); }
-    ~MexpVecs() { g_mexp_cache.park(RIPP_MEXP_BUFS); }
-    MexpVecs(const MexpVecs&) = delete; MexpVecs& operator=(const MexpVecs&) = delete;
-#undef RIPP_MEXP_BUFS
+    VecLease lease{&g_mexp_cache, {&X, &X2, &S, &S2, &KA, &KA2, &jacA, &jacK, &jac2, &qt2, &out, &pA.pow_h, &pA.parts, &pKB.pow_h, &pKB.parts, &pKA.pow_h, &pKA.parts}};      // (last member)
     int32_t reserve(size_t n) {
         int32_t rc;
         if ((rc = X.reserve(2 * n * sizeof(G1A))) || (rc = X2.reserve(2 * n * sizeof(G1A))) || (rc = S.reserve(n * sizeof(Fr))) || (rc = S2.reserve(n * sizeof(Fr))) ||
@@ -24,6 +20,16 @@ struct MexpVecs {
         return RIPP_OK;
     }
 };
+// reserve v for n elements and load an instance from the host: m_a normalised into the upper half of v.X, ck_b below it, ck_a and m_b as they come
+static int32_t mexp_upload(Engine* e, MexpVecs& v, const ripp_g1j* m_a, const ripp_fr* m_b, const ripp_g2a* ck_a, const ripp_g1a* ck_b, size_t n) {
+    int32_t rc; if ((rc = v.reserve(n))) return rc;
+    HIPCHK(hipMemcpyAsync(v.jacA.p, m_a, n * sizeof(G1J), hipMemcpyHostToDevice, e->stream));
+    if ((rc = e->normalize_dev<Fp>(v.jacA.as<G1J>(), n, v.X.as<G1A>() + n))) return rc;
+    HIPCHK(hipMemcpyAsync(v.X.p, ck_b, n * sizeof(G1A), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(v.KA.p, ck_a, n * sizeof(G2A), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(v.S.p, m_b, n * sizeof(Fr), hipMemcpyHostToDevice, e->stream));
+    return e->sync();
+}
 
 // GIPA::_prove (gipa.rs:181-312) on v.X = (ck_b | m_a), v.S = m_b, v.KA = ck_a, n elements each, resident and affine.  Steps and transcript in ROUND order.
 static int32_t gipa_mexp_rounds(Engine* e, MexpVecs& v, size_t n, ripp_gt* com_gt, ripp_g1j* com_ped, ripp_g1j* com_ip, ripp_fr* transcript,
@@ -62,13 +68,13 @@ static int32_t gipa_mexp_rounds(Engine* e, MexpVecs& v, size_t n, ripp_gt* com_g
           gt[0] = final_exponentiation(miller_combine(rows.data())); gt[1] = fut.get(); }
         const G1J ped[2] = {cm[0], cm[2]}, ip[2] = {cm[1], cm[3]};
         const G1A peda[2] = {to_affine(ped[0]), to_affine(ped[1])}, ipa[2] = {to_affine(ip[0]), to_affine(ip[1])};
-        Fr c_inv; const Fr c = fs::gipa_mexp_challenge(round ? &prev_c : nullptr, gt, peda, ipa, c_inv);
+        Fr c_inv; const Fr c = fs::gipa_challenge(round ? &prev_c : nullptr, fs::Com{gt[0], peda[0], ipa[0]}, fs::Com{gt[1], peda[1], ipa[1]}, c_inv);
         e->stats.host_ms += now_ms() - th;
         std::memcpy(&com_gt[2 * round], gt, sizeof gt); std::memcpy(&com_ped[2 * round], ped, sizeof ped); std::memcpy(&com_ip[2 * round], ip, sizeof ip);
         std::memcpy(&transcript[round], &c, sizeof c);
         prev_c = c;
         const double tf = now_ms();
-        rc = folds_with_vm_fallback(e, h, [&]() -> int32_t {
+        rc = fork_join_folds(e, [&]() -> int32_t {
             int32_t r2;
             if ((r2 = fold_dev<Fp>(e, e->stream2, A + h, A, h, c, v.jacA, v.qt2, An, &v.pA))) return r2;                              // m_a  <- m_a_1 * c + m_a_2
             if ((r2 = fold_dev<Fp>(e, e->stream3, KB + h, KB, h, c, v.jacK, v.qt2, KBn, &v.pKB))) return r2;                          // ck_b <- ck_b_1 * c + ck_b_2   (ck_b_1 = ck_b[h:], gipa.rs:216)
@@ -88,22 +94,8 @@ static int32_t gipa_mexp_rounds(Engine* e, MexpVecs& v, size_t n, ripp_gt* com_g
 
 // _compute_recursive_challenges (gipa.rs:322-363) for this instantiation: folds the steps into (ca, cb, ct) = (com_a, com_b, com_t); tr in ROUND order
 static bool gipa_mexp_replay(Fp12& ca, G1J& cb, G1J& ct, const ripp_gt* com_gt, const ripp_g1j* com_ped, const ripp_g1j* com_ip, size_t rounds, std::vector<Fr>& tr) {
-    tr.resize(rounds);
-    for (size_t k = 0; k < rounds; ++k) {
-        const Fp12 gt[2] = {load_gt(&com_gt[2 * k]), load_gt(&com_gt[2 * k + 1])};
-        if (!gt_in_cyclotomic(gt[0]) || !gt_in_cyclotomic(gt[1])) return false;                                          // not a GT element: reject
-        const G1A ped[2] = {to_affine(load_jac<Fp>(&com_ped[2 * k])), to_affine(load_jac<Fp>(&com_ped[2 * k + 1]))};
-        const G1A ip[2] = {to_affine(load_jac<Fp>(&com_ip[2 * k])), to_affine(load_jac<Fp>(&com_ip[2 * k + 1]))};
-        Fr c_inv; const Fr c = fs::gipa_mexp_challenge(k ? &tr[k - 1] : nullptr, gt, ped, ip, c_inv);
-        auto fg = host_pool().submit([&gt, c_inv]() { return gt_pow_host(gt[1], c_inv); });
-        auto fp = host_pool().submit([&ped, c, c_inv]() { return add(smul_host(ped[0], c), smul_host(ped[1], c_inv)); });
-        auto fi = host_pool().submit([&ip, c, c_inv]() { return add(smul_host(ip[0], c), smul_host(ip[1], c_inv)); });
-        const Fp12 g0 = gt_pow_host(gt[0], c);
-        ca = mul(ca, mul(g0, fg.get()));                                                                                 // com + com_1 * c + com_2 * c_inv   (gipa.rs:358-360)
-        cb = add(cb, fp.get()); ct = add(ct, fi.get());
-        tr[k] = c;
-    }
-    return true;
+    return gipa_replay<Fp12, G1A, G1A>(ca, cb, ct, rounds, tr, [&](size_t k, auto& s1, auto& s2) {
+        s1 = {load_gt(&com_gt[2 * k]), load_g1a(&com_ped[2 * k]), load_g1a(&com_ip[2 * k])}; s2 = {load_gt(&com_gt[2 * k + 1]), load_g1a(&com_ped[2 * k + 1]), load_g1a(&com_ip[2 * k + 1])}; });
 }
 }  // extern "C++"
 
@@ -115,12 +107,7 @@ API int32_t ripp_gipa_mexp_prove(const ripp_g1j* m_a, const ripp_fr* m_b, const 
     LOCK; ENGINE;
     e->stats = ripp_stats{};
     const double t_start = now_ms();
-    MexpVecs v; int32_t rc; if ((rc = v.reserve(n))) return rc;
-    HIPCHK(hipMemcpyAsync(v.jacA.p, m_a, n * sizeof(G1J), hipMemcpyHostToDevice, e->stream));
-    if ((rc = e->normalize_dev<Fp>(v.jacA.as<G1J>(), n, v.X.as<G1A>() + n))) return rc;
-    HIPCHK(hipMemcpyAsync(v.X.p, ck_b, n * sizeof(G1A), hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(v.KA.p, ck_a, n * sizeof(G2A), hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(v.S.p, m_b, n * sizeof(Fr), hipMemcpyHostToDevice, e->stream)); if ((rc = e->sync())) return rc;
+    MexpVecs v; int32_t rc; if ((rc = mexp_upload(e, v, m_a, m_b, ck_a, ck_b, n))) return rc;
     G1A ha, hkb; Fr hs; G2A hka;
     if ((rc = gipa_mexp_rounds(e, v, n, com_gt, com_ped, com_ip, transcript, ha, hs, hka, hkb))) return rc;
     const G1J ja = to_jac(ha), jkb = to_jac(hkb); const G2J jka = to_jac(hka);

@@ -7,6 +7,7 @@
 #include <cstdint>
 #include <cstring>
 #include <cstddef>
+#include <initializer_list>
 #include "bls12_381/pairing.hpp"
 #if defined(__x86_64__)
 #include <immintrin.h>
@@ -234,25 +235,59 @@ inline Fr sipp_challenge(FiatShamirRng& rng, const Fp12& z_l, const Fp12& z_r) {
     return fr_from_u128(lo, hi);
 }
 
-// GIPA challenge (ip_proofs/src/gipa.rs:235-258) for the TIPP instantiation: Blake2b over
-//   nonce (usize, big-endian 8 B) || previous challenge (Fr, 32 B LE; Default = 0) || com_1.{0,1,2} || com_2.{0,1,2}
-// where com_x.2 is IdentityOutput(Vec<GT>) => u64-LE length prefix (1) before the element.
-// Returns c = c128^-1 and c_inv = c128 (the reference swaps the names on purpose, :252-256).
-inline Fr gipa_tipp_challenge(const Fr* prev, const Fp12 com[6], Fr& c_inv) {
+// ------------------------------------------------------------------ Blake2b challenges of GIPA / TIPA / aggregate_proofs
+// SSMPlaceholderCommitment (tipa/structured_scalar_message.rs): the commitment of the structured scalar vector, whose image is that of Fr::zero()
+struct SSMPlaceholder {};
+// bytes of the `serialize_uncompressed` image of a transcript member
+template <class T> struct Image;
+template <> struct Image<Fr> { static constexpr size_t N = 32; };
+template <> struct Image<Fp12> { static constexpr size_t N = 576; };
+template <> struct Image<G1A> { static constexpr size_t N = 96; };
+template <> struct Image<G2A> { static constexpr size_t N = 192; };
+template <> struct Image<SSMPlaceholder> { static constexpr size_t N = 32; };
+
+// What one challenge hashes, on the stack (the provers derive one in every latency-bound round: no heap).  Bytes 0..7 belong to the nonce (blake2b_until).
+// CAP is the sum of the members' Image sizes, so put() cannot run over; grow() traps if a caller's sum is wrong.
+template <size_t CAP> struct Transcript {
+    uint8_t buf[CAP]; size_t len = 8;
+    uint8_t* grow(size_t n) { if (n > CAP - len) __builtin_trap(); uint8_t* p = buf + len; len += n; return p; }
+    void put(const Fr& a) { ser_fr(a, grow(32)); }
+    void put(const Fp12& f) { ser_gt(f, grow(576)); }
+    void put(const G1A& p) { ser_g1(p, grow(96)); }          // (the BLS12-377 point layout lives in ser_g1 / ser_g2)
+    void put(const G2A& p) { ser_g2(p, grow(192)); }
+    void put(SSMPlaceholder) { std::memset(grow(32), 0, 32); }
+    void put_len(uint64_t n) { std::memcpy(grow(8), &n, 8); }    // u64-LE length prefix of a Vec
+};
+// The nonce loop of every such challenge: Blake2b-512 over  nonce (usize, big-endian 8 B) || rest of buf  for nonce = 0, 1, .. until accept(digest).
+template <class Accept> inline void blake2b_until(uint8_t* buf, size_t len, Accept&& accept) {
     for (uint64_t nonce = 0;; ++nonce) {
-        uint8_t buf[8 + 32 + 6 * 576 + 16], *p = buf;
-        for (int i = 0; i < 8; ++i) *p++ = (uint8_t)(nonce >> (56 - 8 * i));
-        ser_fr(prev ? *prev : Fr::zero(), p); p += 32;
-        for (int k = 0; k < 6; ++k) {
-            if (k == 2 || k == 5) { const uint64_t one = 1; std::memcpy(p, &one, 8); p += 8; }
-            ser_gt(com[k], p); p += 576;
-        }
-        uint8_t dig[64]; Blake2b h; h.update(buf, (size_t)(p - buf)); h.finish(dig);
+        for (int i = 0; i < 8; ++i) buf[i] = (uint8_t)(nonce >> (56 - 8 * i));
+        uint8_t dig[64]; Blake2b h; h.update(buf, len); h.finish(dig);
+        if (accept(dig)) return;
+    }
+}
+
+// One side of a GIPA round, com_x = (LMC, RMC, IPC) commitments (gipa.rs:209-231).  The five instantiations:
+//   TIPP (groth16_aggregation.rs:36-41)                 (Fp12, Fp12, Fp12)               AFGHO G1, AFGHO G2, Identity<GT>
+//   MIPP, structured scalars (:42-48)                   (Fp12, SSMPlaceholder, G1A)      AFGHO G1, placeholder, Identity<G1>
+//   MIPP, committed scalars (gipa.rs:499-530)           (Fp12, G1A, G1A)                 AFGHO G1, Pedersen<G1>, Identity<G1>
+//   scalar product (tipa/mod.rs:499-526)                (G2A, G1A, Fr)                   Pedersen<G2>, Pedersen<G1>, Identity<Fr>
+//   scalar product, structured (transparent.rs:43-48)   (G1A, SSMPlaceholder, Fr)        Pedersen<G1>, placeholder, Identity<Fr>
+template <class L, class R, class T> struct Com { L l; R r; T t; };
+template <class L, class R, class T> Com(L, R, T) -> Com<L, R, T>;
+// GIPA challenge (gipa.rs:235-258): Blake2b over
+//   nonce || previous challenge (Fr, 32 B LE; Default = 0) || com_1 || com_2,      com_x = l || r || u64 1 || t
+// (the inner-product commitment is IdentityOutput(Vec<_>): a length prefix before its one element, and before it only); the first 128 bits of the
+// digest, big-endian, are taken if non-zero.  Returns c = c128^-1 and c_inv = c128 (the reference swaps the names on purpose, :252-256).
+template <class L, class R, class T> inline Fr gipa_challenge(const Fr* prev, const Com<L, R, T>& com_1, const Com<L, R, T>& com_2, Fr& c_inv) {
+    Transcript<8 + 32 + 2 * (Image<L>::N + Image<R>::N + 8 + Image<T>::N)> w;
+    w.put(prev ? *prev : Fr::zero());
+    for (const Com<L, R, T>* s : {&com_1, &com_2}) { w.put(s->l); w.put(s->r); w.put_len(1); w.put(s->t); }
+    blake2b_until(w.buf, w.len, [&c_inv](const uint8_t dig[64]) {
         uint64_t hi = 0, lo = 0;
         for (int i = 0; i < 8; ++i) { hi = (hi << 8) | dig[i]; lo = (lo << 8) | dig[8 + i]; }
-        const Fr c128 = fr_from_u128(lo, hi);
-        if (!c128.is_zero()) { c_inv = c128; return inv(c128); }
-    }
+        c_inv = fr_from_u128(lo, hi); return !c_inv.is_zero(); });
+    return inv(c_inv);
 }
 
 // Fr::from_random_bytes(&digest) of ark-ff 0.4 (Fp::from_random_bytes_with_flags::<EmptyFlags>): the first 32 bytes are
@@ -268,111 +303,18 @@ inline bool fr_from_random_bytes(const uint8_t dig[64], Fr& out) {
 // KZG challenge point of TIPA (ip_proofs/src/tipa/mod.rs:194-209) and TIPAWithSSM (structured_scalar_message.rs:231-246):
 //   nonce (usize BE) || r_transcript.first() || ck_a_final (G2, uncompressed) [|| ck_b_final (G1)]  -> Blake2b -> from_random_bytes
 inline Fr kzg_challenge(const Fr& first, const G2A& ck_a_final, const G1A* ck_b_final) {
-    for (uint64_t nonce = 0;; ++nonce) {
-        uint8_t buf[8 + 32 + 192 + 96], *p = buf;
-        for (int i = 0; i < 8; ++i) *p++ = (uint8_t)(nonce >> (56 - 8 * i));
-        ser_fr(first, p); p += 32; ser_g2(ck_a_final, p); p += 192;
-        if (ck_b_final) { ser_g1(*ck_b_final, p); p += 96; }
-        uint8_t dig[64]; Blake2b h; h.update(buf, (size_t)(p - buf)); h.finish(dig);
-        Fr c; if (fr_from_random_bytes(dig, c)) return c;
-    }
-}
-
-// GIPA challenge with SSMPlaceholderCommitment on the right and IdentityCommitment<G1> for the inner product
-// (gipa.rs:235-258 instantiated as in groth16_aggregation.rs:42-48): per side  GT (576) || Fr::zero() (32) || u64 1 || G1 (96).
-inline Fr gipa_ssm_challenge(const Fr* prev, const Fp12 gt[2], const G1A g1[2], Fr& c_inv) {
-    for (uint64_t nonce = 0;; ++nonce) {
-        uint8_t buf[8 + 32 + 2 * (576 + 32 + 8 + 96)], *p = buf;
-        for (int i = 0; i < 8; ++i) *p++ = (uint8_t)(nonce >> (56 - 8 * i));
-        ser_fr(prev ? *prev : Fr::zero(), p); p += 32;
-        for (int k = 0; k < 2; ++k) {
-            ser_gt(gt[k], p); p += 576;
-            std::memset(p, 0, 32); p += 32;
-            const uint64_t one = 1; std::memcpy(p, &one, 8); p += 8;
-            ser_g1(g1[k], p); p += 96;
-        }
-        uint8_t dig[64]; Blake2b h; h.update(buf, (size_t)(p - buf)); h.finish(dig);
-        uint64_t hi = 0, lo = 0;
-        for (int i = 0; i < 8; ++i) { hi = (hi << 8) | dig[i]; lo = (lo << 8) | dig[8 + i]; }
-        const Fr c128 = fr_from_u128(lo, hi);
-        if (!c128.is_zero()) { c_inv = c128; return inv(c128); }
-    }
-}
-
-// GIPA challenge with PedersenCommitment<G1> on the right and IdentityCommitment<G1> for the inner product, GIPA<MultiexponentiationInnerProduct<G1>,
-// AFGHOCommitmentG1, PedersenCommitment<G1>, IdentityCommitment<G1>> (gipa.rs:235-258 instantiated as in gipa.rs:499-530): per side
-//   GT (576) || G1 (96) || u64 1 || G1 (96).
-inline Fr gipa_mexp_challenge(const Fr* prev, const Fp12 gt[2], const G1A ped[2], const G1A ip[2], Fr& c_inv) {
-    for (uint64_t nonce = 0;; ++nonce) {
-        uint8_t buf[8 + 32 + 2 * (576 + 96 + 8 + 96)], *p = buf;
-        for (int i = 0; i < 8; ++i) *p++ = (uint8_t)(nonce >> (56 - 8 * i));
-        ser_fr(prev ? *prev : Fr::zero(), p); p += 32;
-        for (int k = 0; k < 2; ++k) {
-            ser_gt(gt[k], p); p += 576;
-            ser_g1(ped[k], p); p += 96;
-            const uint64_t one = 1; std::memcpy(p, &one, 8); p += 8;
-            ser_g1(ip[k], p); p += 96;
-        }
-        uint8_t dig[64]; Blake2b h; h.update(buf, (size_t)(p - buf)); h.finish(dig);
-        uint64_t hi = 0, lo = 0;
-        for (int i = 0; i < 8; ++i) { hi = (hi << 8) | dig[i]; lo = (lo << 8) | dig[8 + i]; }
-        const Fr c128 = fr_from_u128(lo, hi);
-        if (!c128.is_zero()) { c_inv = c128; return inv(c128); }
-    }
-}
-
-// GIPA challenge with PedersenCommitment<G2> on the left, PedersenCommitment<G1> on the right and IdentityCommitment<Fr> for the inner product,
-// TIPA<ScalarInnerProduct, PedersenCommitment<G2>, PedersenCommitment<G1>, IdentityCommitment<Fr>> (gipa.rs:235-258 instantiated as in tipa/mod.rs:499-526):
-// per side  G2 (192) || G1 (96) || u64 1 || Fr (32).
-inline Fr gipa_scalar_challenge(const Fr* prev, const G2A g2[2], const G1A g1[2], const Fr ip[2], Fr& c_inv) {
-    for (uint64_t nonce = 0;; ++nonce) {
-        uint8_t buf[8 + 32 + 2 * (192 + 96 + 8 + 32)], *p = buf;
-        for (int i = 0; i < 8; ++i) *p++ = (uint8_t)(nonce >> (56 - 8 * i));
-        ser_fr(prev ? *prev : Fr::zero(), p); p += 32;
-        for (int k = 0; k < 2; ++k) {
-            ser_g2(g2[k], p); p += 192;
-            ser_g1(g1[k], p); p += 96;
-            const uint64_t one = 1; std::memcpy(p, &one, 8); p += 8;
-            ser_fr(ip[k], p); p += 32;
-        }
-        uint8_t dig[64]; Blake2b h; h.update(buf, (size_t)(p - buf)); h.finish(dig);
-        uint64_t hi = 0, lo = 0;
-        for (int i = 0; i < 8; ++i) { hi = (hi << 8) | dig[i]; lo = (lo << 8) | dig[8 + i]; }
-        const Fr c128 = fr_from_u128(lo, hi);
-        if (!c128.is_zero()) { c_inv = c128; return inv(c128); }
-    }
-}
-
-// GIPA challenge of the first tier of the transparent polynomial commitment, GIPAWithSSM<ScalarInnerProduct, PedersenCommitment<G1>,
-// IdentityCommitment<Fr>> (transparent.rs:43-48; gipa.rs:235-258): per side  G1 (96) || Fr::zero() (32) || u64 1 || Fr (32).
-inline Fr gipa_scalar_ssm_challenge(const Fr* prev, const G1A g1[2], const Fr ip[2], Fr& c_inv) {
-    for (uint64_t nonce = 0;; ++nonce) {
-        uint8_t buf[8 + 32 + 2 * (96 + 32 + 8 + 32)], *p = buf;
-        for (int i = 0; i < 8; ++i) *p++ = (uint8_t)(nonce >> (56 - 8 * i));
-        ser_fr(prev ? *prev : Fr::zero(), p); p += 32;
-        for (int k = 0; k < 2; ++k) {
-            ser_g1(g1[k], p); p += 96;
-            std::memset(p, 0, 32); p += 32;
-            const uint64_t one = 1; std::memcpy(p, &one, 8); p += 8;
-            ser_fr(ip[k], p); p += 32;
-        }
-        uint8_t dig[64]; Blake2b h; h.update(buf, (size_t)(p - buf)); h.finish(dig);
-        uint64_t hi = 0, lo = 0;
-        for (int i = 0; i < 8; ++i) { hi = (hi << 8) | dig[i]; lo = (lo << 8) | dig[8 + i]; }
-        const Fr c128 = fr_from_u128(lo, hi);
-        if (!c128.is_zero()) { c_inv = c128; return inv(c128); }
-    }
+    Transcript<8 + 32 + 192 + 96> w; Fr c;
+    w.put(first); w.put(ck_a_final); if (ck_b_final) w.put(*ck_b_final);
+    blake2b_until(w.buf, w.len, [&c](const uint8_t dig[64]) { return fr_from_random_bytes(dig, c); });
+    return c;
 }
 
 // random-linear-combination challenge of aggregate_proofs (groth16_aggregation.rs:105-116)
 inline Fr aggregation_challenge(const Fp12& com_a, const Fp12& com_b, const Fp12& com_c) {
-    for (uint64_t nonce = 0;; ++nonce) {
-        uint8_t buf[8 + 3 * 576], *p = buf;
-        for (int i = 0; i < 8; ++i) *p++ = (uint8_t)(nonce >> (56 - 8 * i));
-        ser_gt(com_a, p); p += 576; ser_gt(com_b, p); p += 576; ser_gt(com_c, p); p += 576;
-        uint8_t dig[64]; Blake2b h; h.update(buf, (size_t)(p - buf)); h.finish(dig);
-        Fr r; if (fr_from_random_bytes(dig, r)) return r;
-    }
+    Transcript<8 + 3 * 576> w; Fr r;
+    w.put(com_a); w.put(com_b); w.put(com_c);
+    blake2b_until(w.buf, w.len, [&r](const uint8_t dig[64]) { return fr_from_random_bytes(dig, r); });
+    return r;
 }
 
 }}  // namespace ripp::fs

@@ -9,16 +9,23 @@ extern "C++" {
 // second base of a fold in the VM regime (vm_fold2.hpp): 2^64 hi (G1) / 2^32 hi (G2) in projective form, prepared while the host
 // finishes the round's GT values; `ready` is consumed by the next fold_dev on the same vector
 struct FoldPre { DevBuf pow_h, parts; bool ready = false; void release() { pow_h.release(); parts.release(); } };
-// The per-call vector sets below (TippVecs / SsmVecs) hand their device buffers to one of these when they go out of scope and the next set adopts them:
+// The per-call vector sets (TippVecs / SsmVecs / MexpVecs / ScalVecs) hand their device buffers to one of these when they go out of scope and the next set adopts them:
 // a call of aggregate_proofs at n = 2^14 made ~35 hipMalloc / hipFree pairs, and a hipFree of >= 1 MB costs 60-120 us on this runtime (2-4 ms per call).
 // Freed by ripp_release_scratch / ripp_shutdown (vec_caches_release).  All users hold the engine lock.
 struct VecBufCache { std::vector<DevBuf> bufs; bool full = false;
-    void adopt(std::initializer_list<DevBuf*> l) { if (!full || bufs.size() != l.size()) return; size_t i = 0; for (DevBuf* b : l) std::swap(*b, bufs[i++]); full = false; }
+    void adopt(const std::vector<DevBuf*>& l) { if (!full || bufs.size() != l.size()) return; size_t i = 0; for (DevBuf* b : l) std::swap(*b, bufs[i++]); full = false; }
     // park() synchronises the device first: a prover that returns early on an error may leave kernels of this call in flight on the engine's (or
     // the auxiliary engine's) streams, and the next call adopts the same buffers, possibly on other streams.  ~10 us on an idle device, once per call.
-    void park(std::initializer_list<DevBuf*> l) { (void)hipDeviceSynchronize(); if (full) { for (DevBuf* b : l) b->release(); return; } bufs.resize(l.size()); size_t i = 0; for (DevBuf* b : l) { bufs[i].release(); std::swap(*b, bufs[i++]); } full = true; }
+    void park(const std::vector<DevBuf*>& l) { (void)hipDeviceSynchronize(); if (full) { for (DevBuf* b : l) b->release(); return; } bufs.resize(l.size()); size_t i = 0; for (DevBuf* b : l) { bufs[i].release(); std::swap(*b, bufs[i++]); } full = true; }
     void release() { for (DevBuf& b : bufs) b.release(); full = false; } };
 static VecBufCache g_tipp_cache, g_ssm_cache, g_mexp_cache, g_scal_cache;      // (g_mexp_cache: the vector set of gipa_mexp_api.inc and tipa_mexp_api.inc, g_scal_cache: that of tipa_scalar_api.inc)
+// A vector set's hold on its buffers: adopts the cache's parked buffers when the set is built and parks them when it goes.  cache == nullptr: the set of one
+// in-process rank (its own device: never into the process-wide parking place), synchronised and released instead.  Declare it as the LAST member of the set:
+// members die in reverse order, so the lease parks while the DevBufs are still alive (as a base class it would run after they are gone).
+struct VecLease { VecBufCache* cache; std::vector<DevBuf*> bufs;
+    VecLease(VecBufCache* c, std::initializer_list<DevBuf*> l) : cache(c), bufs(l) { if (cache) cache->adopt(bufs); }
+    ~VecLease() { if (cache) cache->park(bufs); else { (void)hipDeviceSynchronize(); for (DevBuf* b : bufs) b->release(); } }
+    VecLease(const VecLease&) = delete; VecLease& operator=(const VecLease&) = delete; };
 static FoldPre g_tpc_pre;                  // second fold base of the first-tier key folds (tpc_api.inc)
 static void vec_caches_release() { g_tipp_cache.release(); g_ssm_cache.release(); g_mexp_cache.release(); g_scal_cache.release(); g_tpc_pre.release(); }
 template <class F> static int32_t fold_precompute(Engine* e, hipStream_t st, const Affine<F>* hi, size_t half, FoldPre& fp) {
@@ -95,7 +102,7 @@ template <> int32_t fold_dev<Fp2>(Engine* e, hipStream_t st, const G2A* hi, cons
     if (fp) fp->ready = false;
     const size_t qstride = (half + 63) & ~(size_t)63;
     const size_t qt_bytes = std::max<size_t>(4 * G2A_CHUNKS * qstride * sizeof(uint4), 4 * half * sizeof(G2J));
-    if ((rc = qt.reserve(qt_bytes + 4 * half + 16))) return rc;          // (+ one flag byte per lane of the carry-free GLS fold, behind the parts: this call's own scratch, the two G2 folds of a round may run side by side)
+    if ((rc = qt.reserve(qt_bytes + 4 * half + 16)) || (rc = e->vm_flag.reserve(sizeof(uint32_t)))) return rc;          // (vm_flag: a vestigial argument of k_vm_fold_g2_split; + one flag byte per lane of the carry-free GLS fold, behind the parts: this call's own scratch, the two G2 folds of a round may run side by side)
     if (half <= e->vm_fold_max && !e->sw.no_vm) {
         hipLaunchKernelGGL(k_vm_fold_g2_split, dim3(nblk(half, 4 * VM_EPW), 4), dim3(256), 4 * VM_EPW * VM_G2_SLOTS * sizeof(VmSlot), st, hi, (uint32_t)half, gls_digits(s), qt.as<G2J>(), e->vm_flag.as<uint32_t>());
         hipLaunchKernelGGL(k_vm_combine_g2, dim3(nblk(half, 4 * VM_EPW)), dim3(256), 4 * VM_EPW * VM_G2_SLOTS * sizeof(VmSlot), st, qt.as<G2J>(), lo, (uint32_t)half, jac.as<G2J>());
@@ -153,12 +160,10 @@ struct TippVecs {
     DevBuf A, A2, KB, KB2, B, B2, KA, KA2, jac1, jac1b, jac2, jac2b, qt2;
     DevBuf AU, AU2, jac1u;                 // implicit-shift form (aggregate_proofs): the UNSCALED left vector beside the scaled one
     FoldPre pA, pKB, pB, pKA, pAU;         // second fold bases of the small rounds
-#define RIPP_TIPP_BUFS {&A, &A2, &KB, &KB2, &B, &B2, &KA, &KA2, &jac1, &jac1b, &jac2, &jac2b, &qt2, &AU, &AU2, &jac1u, &pA.pow_h, &pA.parts, &pKB.pow_h, &pKB.parts, &pB.pow_h, &pB.parts, &pKA.pow_h, &pKA.parts, &pAU.pow_h, &pAU.parts}
-    const bool cached;                     // false: the buffers of one in-process rank (its own device: never into the process-wide parking place)
-    explicit TippVecs(bool use_cache = true) : cached(use_cache) { if (cached) g_tipp_cache.adopt(RIPP_TIPP_BUFS); }
-    ~TippVecs() { if (cached) g_tipp_cache.park(RIPP_TIPP_BUFS); else { (void)hipDeviceSynchronize(); for (DevBuf* b : RIPP_TIPP_BUFS) b->release(); } }
-    TippVecs(const TippVecs&) = delete; TippVecs& operator=(const TippVecs&) = delete;
-#undef RIPP_TIPP_BUFS
+    VecLease lease;                        // (last member)
+    explicit TippVecs(bool use_cache = true)      // false: the buffers of one in-process rank
+        : lease(use_cache ? &g_tipp_cache : nullptr, {&A, &A2, &KB, &KB2, &B, &B2, &KA, &KA2, &jac1, &jac1b, &jac2, &jac2b, &qt2, &AU, &AU2, &jac1u, &pA.pow_h, &pA.parts, &pKB.pow_h, &pKB.parts,
+                                                       &pB.pow_h, &pB.parts, &pKA.pow_h, &pKA.parts, &pAU.pow_h, &pAU.parts}) {}
     int32_t reserve(size_t n) {
         int32_t rc;
         for (DevBuf* b : {&A, &A2, &KB, &KB2}) if ((rc = b->reserve(n * sizeof(G1A)))) return rc;
@@ -169,22 +174,16 @@ struct TippVecs {
 };
 
 extern "C++" {
-// run one set of folds on the two streams; on an exceptional addition reported by a VM fold, redo with the complete scalar kernels
-template <class Launch> static int32_t folds_with_vm_fallback(Engine* e, size_t split, Launch&& launch) {
+// one round's folds: the four side streams wait for the engine's stream, `launch` enqueues the folds on whichever of the five it likes, the engine's stream
+// waits for all of them and is synchronised.  (The VM folds use the complete addition law: there is no exceptional case to detect and redo.)
+template <class Launch> static int32_t fork_join_folds(Engine* e, Launch&& launch) {
     int32_t rc;
-    const size_t saved_vm_max = e->vm_fold_max;
-    if ((rc = e->vm_flag.reserve(sizeof(uint32_t)))) return rc;
-    for (;;) {
-        HIPCHK(hipEventRecord(e->ev_fork, e->stream));
-        for (hipStream_t st : {e->stream2, e->stream3, e->stream4, e->stream5}) HIPCHK(hipStreamWaitEvent(st, e->ev_fork, 0));
-        if ((rc = launch())) { e->vm_fold_max = saved_vm_max; return rc; }
-        HIPCHK(hipEventRecord(e->ev_join, e->stream2)); HIPCHK(hipEventRecord(e->ev_join3, e->stream3)); HIPCHK(hipEventRecord(e->ev_join4, e->stream4)); HIPCHK(hipEventRecord(e->ev_join5, e->stream5));
-        for (hipEvent_t ev : {e->ev_join, e->ev_join3, e->ev_join4, e->ev_join5}) HIPCHK(hipStreamWaitEvent(e->stream, ev, 0));
-        if ((rc = e->sync())) { e->vm_fold_max = saved_vm_max; return rc; }
-        break;      // the VM folds use the complete addition law: no exceptional case to redo (the flag word is a vestigial kernel argument)
-    }
-    e->vm_fold_max = saved_vm_max;
-    return RIPP_OK;
+    HIPCHK(hipEventRecord(e->ev_fork, e->stream));
+    for (hipStream_t st : {e->stream2, e->stream3, e->stream4, e->stream5}) HIPCHK(hipStreamWaitEvent(st, e->ev_fork, 0));
+    if ((rc = launch())) return rc;
+    HIPCHK(hipEventRecord(e->ev_join, e->stream2)); HIPCHK(hipEventRecord(e->ev_join3, e->stream3)); HIPCHK(hipEventRecord(e->ev_join4, e->stream4)); HIPCHK(hipEventRecord(e->ev_join5, e->stream5));
+    for (hipEvent_t ev : {e->ev_join, e->ev_join3, e->ev_join4, e->ev_join5}) HIPCHK(hipStreamWaitEvent(e->stream, ev, 0));
+    return e->sync();
 }
 }  // extern "C++"
 
@@ -320,14 +319,14 @@ static int32_t gipa_tipp_core(Engine* e, TippVecs& v, size_t n, ripp_gt* com_ste
           Fp12 zs[6]; zs[0] = z0;
           for (int k = 1; k < 6; ++k) zs[k] = fut[k - 1].get();
           for (int k = 0; k < 6; ++k) com[k] = zs[k]; }
-        Fr c_inv; const Fr c = fs::gipa_tipp_challenge(round ? &prev_c : nullptr, com, c_inv);
+        Fr c_inv; const Fr c = fs::gipa_challenge(round ? &prev_c : nullptr, fs::Com{com[0], com[1], com[2]}, fs::Com{com[3], com[4], com[5]}, c_inv);
         const Fr c_u = shift ? mul(c, rp[lg_split]) : c, c_inv_u = shift ? mul(c_inv, rpi[lg_split]) : c_inv;   // fold scalars of the unscaled vectors
         e->stats.host_ms += now_ms() - th;
         std::memcpy(&com_steps[6 * round], com, sizeof com); std::memcpy(&transcript[round], &c, sizeof c);
         prev_c = c;
         // folds (gipa.rs:262-290): hi = upper half, lo = lower half for all four vectors
         const double tf = now_ms();
-        rc = folds_with_vm_fallback(e, split, [&]() -> int32_t {
+        rc = fork_join_folds(e, [&]() -> int32_t {
             int32_t r2;
             if (batch && v.pA.ready && v.pB.ready) {                                  // same scalars and operands as the five calls below
                 rq1[0].s = c; rq1[1].s = c; rq1[2].s = c_u; rq2[0].s = c_inv; rq2[1].s = c_inv_u;
@@ -594,11 +593,7 @@ API int32_t ripp_tipa_tipp_prove(const ripp_srs* srs, const ripp_g1j* m_a, const
 struct SsmVecs {
     DevBuf A, A2, S, S2, KA, KA2, jac1, jac2, qt2;
     FoldPre pA, pKA;                        // second fold bases of the small rounds
-#define RIPP_SSM_BUFS {&A, &A2, &S, &S2, &KA, &KA2, &jac1, &jac2, &qt2, &pA.pow_h, &pA.parts, &pKA.pow_h, &pKA.parts}
-    SsmVecs() { g_ssm_cache.adopt(RIPP_SSM_BUFS); }
-    ~SsmVecs() { g_ssm_cache.park(RIPP_SSM_BUFS); }
-    SsmVecs(const SsmVecs&) = delete; SsmVecs& operator=(const SsmVecs&) = delete;
-#undef RIPP_SSM_BUFS
+    VecLease lease{&g_ssm_cache, {&A, &A2, &S, &S2, &KA, &KA2, &jac1, &jac2, &qt2, &pA.pow_h, &pA.parts, &pKA.pow_h, &pKA.parts}};      // (last member)
     int32_t reserve(size_t n) {
         int32_t rc;
         if ((rc = A.reserve(n * sizeof(G1A))) || (rc = A2.reserve(n * sizeof(G1A))) || (rc = S.reserve(n * sizeof(Fr))) || (rc = S2.reserve(n * sizeof(Fr))) ||
@@ -653,12 +648,12 @@ static int32_t tipa_ssm_rounds(Engine* e, SsmVecs& v, size_t n, ripp_gt* com_gt,
         { auto fut = host_pool().submit([&rows]() { return final_exponentiation(miller_combine(rows.data() + N_LINES)); });
           gt[0] = final_exponentiation(miller_combine(rows.data())); gt[1] = fut.get(); }
         const G1A ipa[2] = {to_affine(ip[0]), to_affine(ip[1])};
-        Fr c_inv; const Fr c = fs::gipa_ssm_challenge(round ? &prev_c : nullptr, gt, ipa, c_inv);
+        Fr c_inv; const Fr c = fs::gipa_challenge(round ? &prev_c : nullptr, fs::Com{gt[0], fs::SSMPlaceholder{}, ipa[0]}, fs::Com{gt[1], fs::SSMPlaceholder{}, ipa[1]}, c_inv);
         e->stats.host_ms += now_ms() - th;
         std::memcpy(&com_gt[2 * round], gt, sizeof gt); std::memcpy(&com_g1[2 * round], ip, sizeof ip); std::memcpy(&transcript[round], &c, sizeof c);
         prev_c = c;
         const double tf = now_ms();
-        rc = folds_with_vm_fallback(e, split, [&]() -> int32_t {
+        rc = fork_join_folds(e, [&]() -> int32_t {
             int32_t r2;
             if ((r2 = fold_dev<Fp>(e, e->stream2, A + split, A, split, c, v.jac1, v.qt2, v.A2.as<G1A>(), &v.pA))) return r2;       // m_a  <- m_a_1 * c + m_a_2
             hipLaunchKernelGGL(k_fold_fr, dim3(nblk(split, 256)), dim3(256), 0, e->stream3, S + split, S, (uint32_t)split, c_inv, v.S2.as<Fr>());   // m_b  <- m_b_2 * c_inv + m_b_1
@@ -913,37 +908,58 @@ static int32_t kzg_verify_g1(Engine* e, const VSrs& v, const G1J& ck_final, cons
     const G2J r2 = add(v.h_alpha, neg(smul_host(to_affine(v.h), c)));
     return pairing_eq(e, l1, v.h, opening, r2, ok);
 }
-// _compute_recursive_challenges (gipa.rs:322-363), TIPP instantiation; tr in ROUND order
-static bool tipp_replay(const ripp_gt com[3], const ripp_gt* com_steps, size_t rounds, std::vector<Fr>& tr, Fp12 out[3]) {
-    Fp12 acc[3] = {load_gt(&com[0]), load_gt(&com[1]), load_gt(&com[2])};
+// ---- _compute_recursive_challenges (gipa.rs:322-363), one replay for every instantiation ----
+// A commitment component is folded as  acc <- acc + c x_1 + c_inv x_2  (gipa.rs:358-360) in its own group: GT multiplicatively, G1 / G2 / Fr additively, the
+// SSM placeholder not at all.  com_term is one k x, com_add the accumulation; a proof's points travel affine (their byte image is hashed), the sums Jacobian.
+static Fp12 com_term(const Fp12& x, const Fr& k) { return gt_pow_host(x, k); }
+template <class F> static Jac<F> com_term(const Affine<F>& x, const Fr& k) { return smul_host(x, k); }
+static Fr com_term(const Fr& x, const Fr& k) { return mul(x, k); }
+static fs::SSMPlaceholder com_term(fs::SSMPlaceholder x, const Fr&) { return x; }
+static void com_add(Fp12& acc, const Fp12& t) { acc = mul(acc, t); }
+template <class F> static void com_add(Jac<F>& acc, const Jac<F>& t) { acc = add(acc, t); }
+static void com_add(Fr& acc, const Fr& t) { acc = add(acc, t); }
+static void com_add(fs::SSMPlaceholder&, fs::SSMPlaceholder) {}
+template <class X> using ComAcc = decltype(com_term(std::declval<const X&>(), std::declval<const Fr&>()));
+// a term beside the calling thread: an exponentiation or scalar multiplication goes to the host pool, a field product is done at once.
+// x and k are captured by reference: get() before they go out of scope.
+template <class X> struct ComTermAsync {
+    std::future<ComAcc<X>> f; ComAcc<X> v;
+    ComTermAsync(const X& x, const Fr& k) {
+        if constexpr (std::is_same<X, Fr>::value || std::is_same<X, fs::SSMPlaceholder>::value) v = com_term(x, k);
+        else f = host_pool().submit([&x, &k]() { return com_term(x, k); });
+    }
+    ComAcc<X> get() { return f.valid() ? f.get() : v; }
+};
+static bool com_member_ok(const Fp12& x) { return gt_in_cyclotomic(x); }      // not a GT element: reject (gt_pow_host is only an exponentiation in the cyclotomic subgroup)
+template <class X> static bool com_member_ok(const X&) { return true; }
+// Folds the steps of `rounds` rounds into (al, ar, at) = (com_a, com_b, com_t) and writes the challenges to tr in ROUND order.  load(k, com_1, com_2) fills round
+// k's members.  false: a GT member is not in the cyclotomic subgroup (found before anything of that round is exponentiated).  Of a round's up to six
+// exponentiations / scalar multiplications the first (c com_1.l: costly in every instantiation) runs here, the others on pool threads.
+template <class L, class R, class T, class Load> static bool gipa_replay(ComAcc<L>& al, ComAcc<R>& ar, ComAcc<T>& at, size_t rounds, std::vector<Fr>& tr, Load&& load) {
     tr.resize(rounds);
     for (size_t k = 0; k < rounds; ++k) {
-        Fp12 s[6]; std::memcpy(s, &com_steps[6 * k], sizeof s);
-        for (int j = 0; j < 6; ++j) if (!gt_in_cyclotomic(s[j])) return false;          // not a GT element: reject
-        Fr c_inv; const Fr c = fs::gipa_tipp_challenge(k ? &tr[k - 1] : nullptr, s, c_inv);
-        std::future<Fp12> f[5];
-        for (int j = 1; j < 6; ++j) f[j - 1] = host_pool().submit([&s, j, c, c_inv]() { return gt_pow_host(s[j], j < 3 ? c : c_inv); });
-        Fp12 p[6]; p[0] = gt_pow_host(s[0], c); for (int j = 1; j < 6; ++j) p[j] = f[j - 1].get();
-        for (int j = 0; j < 3; ++j) acc[j] = mul(acc[j], mul(p[j], p[j + 3]));       // com + com_1 * c + com_2 * c_inv  (gipa.rs:358-360)
+        fs::Com<L, R, T> s1, s2; load(k, s1, s2);
+        for (const fs::Com<L, R, T>* s : {&s1, &s2}) if (!com_member_ok(s->l) || !com_member_ok(s->r) || !com_member_ok(s->t)) return false;
+        Fr c_inv; const Fr c = fs::gipa_challenge(k ? &tr[k - 1] : nullptr, s1, s2, c_inv);
+        ComTermAsync<L> l2(s2.l, c_inv); ComTermAsync<R> r1(s1.r, c), r2(s2.r, c_inv); ComTermAsync<T> t1(s1.t, c), t2(s2.t, c_inv);
+        const ComAcc<L> l1 = com_term(s1.l, c);
+        com_add(al, l1); com_add(al, l2.get()); com_add(ar, r1.get()); com_add(ar, r2.get()); com_add(at, t1.get()); com_add(at, t2.get());
         tr[k] = c;
     }
-    out[0] = acc[0]; out[1] = acc[1]; out[2] = acc[2];
     return true;
 }
-// the same for the second-tier GIPAWithSSM instantiation (MultiexponentiationInnerProduct<G1>, AFGHO commitment): folds the steps into (ca, ct) = (com_a, com_t)
+static G1A load_g1a(const ripp_g1j* p) { return to_affine(load_jac<Fp>(p)); }
+static G2A load_g2a(const ripp_g2j* p) { return to_affine(load_jac<Fp2>(p)); }
+// TIPP: com_steps[k] = com_1.{0,1,2}, com_2.{0,1,2}
+static bool tipp_replay(const ripp_gt com[3], const ripp_gt* com_steps, size_t rounds, std::vector<Fr>& tr, Fp12 out[3]) {
+    for (int j = 0; j < 3; ++j) out[j] = load_gt(&com[j]);
+    return gipa_replay<Fp12, Fp12, Fp12>(out[0], out[1], out[2], rounds, tr, [&](size_t k, auto& s1, auto& s2) { std::memcpy(&s1, &com_steps[6 * k], sizeof s1); std::memcpy(&s2, &com_steps[6 * k + 3], sizeof s2); });
+}
+// the second-tier GIPAWithSSM instantiation (MultiexponentiationInnerProduct<G1>, AFGHO commitment): folds the steps into (ca, ct) = (com_a, com_t)
 static bool ssm_replay(Fp12& ca, G1J& ct, const ripp_gt* com_gt, const ripp_g1j* com_g1, size_t rounds, std::vector<Fr>& tr) {
-    tr.resize(rounds);
-    for (size_t k = 0; k < rounds; ++k) {                                                                                // gipa.rs:329-360
-        const Fp12 gt[2] = {load_gt(&com_gt[2 * k]), load_gt(&com_gt[2 * k + 1])};
-        if (!gt_in_cyclotomic(gt[0]) || !gt_in_cyclotomic(gt[1])) return false;                                          // not a GT element: reject
-        const G1A g1[2] = {to_affine(load_jac<Fp>(&com_g1[2 * k])), to_affine(load_jac<Fp>(&com_g1[2 * k + 1]))};
-        Fr c_inv; const Fr c = fs::gipa_ssm_challenge(k ? &tr[k - 1] : nullptr, gt, g1, c_inv);
-        auto f = host_pool().submit([&gt, c_inv]() { return gt_pow_host(gt[1], c_inv); });
-        ca = mul(ca, mul(gt_pow_host(gt[0], c), f.get()));
-        ct = add(add(ct, smul_host(g1[0], c)), smul_host(g1[1], c_inv));
-        tr[k] = c;
-    }
-    return true;
+    fs::SSMPlaceholder cb;
+    return gipa_replay<Fp12, fs::SSMPlaceholder, G1A>(ca, cb, ct, rounds, tr, [&](size_t k, auto& s1, auto& s2) {
+        s1 = {load_gt(&com_gt[2 * k]), {}, load_g1a(&com_g1[2 * k])}; s2 = {load_gt(&com_gt[2 * k + 1]), {}, load_g1a(&com_g1[2 * k + 1])}; });
 }
 // exponents of _compute_final_commitment_keys (gipa.rs:365-399) by doubling over the reversed transcript (tr in ROUND order): powers of c^-1 for ck_a, of c for ck_b
 static std::vector<Fr> final_key_exponents(const std::vector<Fr>& tr, bool inverse) {
@@ -961,6 +977,21 @@ static Fr ssm_b_base(const std::vector<Fr>& tr, const Fr& scalar_b) {
     Fr p2b = scalar_b, bb = Fr::one();
     for (size_t i = 0; i < tr.size(); ++i) { bb = mul(bb, add(Fr::one(), mul(inv(tr[tr.size() - 1 - i]), p2b))); p2b = mul(p2b, p2b); }
     return bb;
+}
+// What TIPA::verify_with_srs_shift does between the replay and the base check, for every instantiation (tipa/mod.rs:252-289): the KZG challenge from the last
+// round's challenge and both final keys, the opening check of ck_a (inverse transcript, shift r_shift^-1) and of ck_b.  trf: the replayed transcript in ROUND
+// order.  *ok = both openings hold; kaa, kba: the affine final keys, which the caller's base check needs.
+static int32_t tipa_verify_tail(Engine* e, const ripp_verifier_srs* v_srs, const std::vector<Fr>& trf, const ripp_g2j* final_ck_a, const ripp_g1j* final_ck_b,
+                                const ripp_g2j* opening_a, const ripp_g1j* opening_b, const ripp_fr* r_shift, G2A& kaa, G1A& kba, bool* ok) {
+    const VSrs v = load_vsrs(v_srs); const size_t rounds = trf.size();
+    std::vector<Fr> tr(rounds), tri(rounds); for (size_t i = 0; i < rounds; ++i) { tr[i] = trf[rounds - 1 - i]; tri[i] = inv(tr[i]); }
+    const G2J ka = load_jac<Fp2>(final_ck_a), oa = load_jac<Fp2>(opening_a); const G1J kb = load_jac<Fp>(final_ck_b), ob = load_jac<Fp>(opening_b);
+    kaa = to_affine(ka); kba = to_affine(kb);
+    const Fr c = fs::kzg_challenge(tr[0], kaa, &kba);                                                                    // :257-272
+    bool ok_a = false, ok_b = false; int32_t rc;
+    if ((rc = kzg_verify_g2(e, v, ka, oa, tri, inv(load_fr(r_shift)), c, &ok_a))) return rc;                             // :274-281
+    if ((rc = kzg_verify_g1(e, v, kb, ob, tr, Fr::one(), c, &ok_b))) return rc;                                          // :282-289
+    *ok = ok_a && ok_b; return RIPP_OK;
 }
 }  // extern "C++"
 
@@ -987,20 +1018,14 @@ API int32_t ripp_tipa_tipp_verify(const ripp_verifier_srs* v_srs, const ripp_gt 
                                   const ripp_g2j* opening_a, const ripp_g1j* opening_b, const ripp_fr* r_shift, int32_t* accept) {
     if (!v_srs || !com || !com_steps || !base_a || !base_b || !final_ck_a || !final_ck_b || !opening_a || !opening_b || !r_shift || !accept || rounds == 0) return RIPP_ERR_ARG;
     LOCK; ENGINE;
-    const VSrs v = load_vsrs(v_srs);
     std::vector<Fr> trf; Fp12 bc[3];
     if (!tipp_replay(com, com_steps, rounds, trf, bc)) { *accept = 0; return RIPP_OK; }                                  // :249-251
-    std::vector<Fr> tr(rounds), tri(rounds); for (size_t i = 0; i < rounds; ++i) { tr[i] = trf[rounds - 1 - i]; tri[i] = inv(tr[i]); }
-    const G2J ka = load_jac<Fp2>(final_ck_a), oa = load_jac<Fp2>(opening_a); const G1J kb = load_jac<Fp>(final_ck_b), ob = load_jac<Fp>(opening_b);
-    const G2A kaa = to_affine(ka); const G1A kba = to_affine(kb);
-    const Fr c = fs::kzg_challenge(tr[0], kaa, &kba);                                                                    // :257-272
-    bool ok_a = false, ok_b = false; int32_t rc;
-    if ((rc = kzg_verify_g2(e, v, ka, oa, tri, inv(load_fr(r_shift)), c, &ok_a))) return rc;                             // :274-281
-    if ((rc = kzg_verify_g1(e, v, kb, ob, tr, Fr::one(), c, &ok_b))) return rc;                                          // :282-289
-    const G1A a = to_affine(load_jac<Fp>(base_a)); const G2A b = to_affine(load_jac<Fp2>(base_b));
+    G2A kaa; G1A kba; bool ok = false; int32_t rc;
+    if ((rc = tipa_verify_tail(e, v_srs, trf, final_ck_a, final_ck_b, opening_a, opening_b, r_shift, kaa, kba, &ok))) return rc;
+    const G1A a = load_g1a(base_a); const G2A b = load_g2a(base_b);
     Fp12 e1, e2, e3;                                                                                                     // :292-298
     if ((rc = pairing_host_pts(e, {a}, {kaa}, &e1)) || (rc = pairing_host_pts(e, {kba}, {b}, &e2)) || (rc = pairing_host_pts(e, {a}, {b}, &e3))) return rc;
-    *accept = (ok_a && ok_b && e1 == bc[0] && e2 == bc[1] && e3 == bc[2]) ? 1 : 0;
+    *accept = (ok && e1 == bc[0] && e2 == bc[1] && e3 == bc[2]) ? 1 : 0;
     return RIPP_OK;
 }
 

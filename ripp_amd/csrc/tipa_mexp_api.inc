@@ -15,12 +15,7 @@ API int32_t ripp_tipa_mexp_prove(const ripp_srs* srs, const ripp_g1j* m_a, const
     LOCK; ENGINE;
     e->stats = ripp_stats{};
     const double t_start = now_ms();
-    MexpVecs v; int32_t rc; if ((rc = v.reserve(n))) return rc;
-    HIPCHK(hipMemcpyAsync(v.jacA.p, m_a, n * sizeof(G1J), hipMemcpyHostToDevice, e->stream));
-    if ((rc = e->normalize_dev<Fp>(v.jacA.as<G1J>(), n, v.X.as<G1A>() + n))) return rc;
-    HIPCHK(hipMemcpyAsync(v.X.p, ck_b, n * sizeof(G1A), hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(v.KA.p, ck_a, n * sizeof(G2A), hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(v.S.p, m_b, n * sizeof(Fr), hipMemcpyHostToDevice, e->stream)); if ((rc = e->sync())) return rc;
+    MexpVecs v; int32_t rc; if ((rc = mexp_upload(e, v, m_a, m_b, ck_a, ck_b, n))) return rc;
     G1A ha, hkb; Fr hs; G2A hka;
     if ((rc = gipa_mexp_rounds(e, v, n, com_gt, com_ped, com_ip, transcript, ha, hs, hka, hkb))) return rc;                 // mod.rs:184-188
     G2J oa; G1J ob; Fr c;
@@ -38,19 +33,13 @@ API int32_t ripp_tipa_mexp_verify(const ripp_verifier_srs* v_srs, const ripp_gt*
     if (!v_srs || !com_a || !com_b || !com_t || !com_gt || !com_ped || !com_ip || !base_a || !base_b || !final_ck_a || !final_ck_b || !opening_a || !opening_b ||
         !r_shift || !accept || rounds == 0 || rounds > 24) return RIPP_ERR_ARG;
     LOCK; ENGINE;
-    const VSrs v = load_vsrs(v_srs);
     Fp12 ca = load_gt(com_a); G1J cb = load_jac<Fp>(com_b), ct = load_jac<Fp>(com_t);
     std::vector<Fr> trf;
     if (!gipa_mexp_replay(ca, cb, ct, com_gt, com_ped, com_ip, rounds, trf)) { *accept = 0; return RIPP_OK; }                // mod.rs:249-251
-    std::vector<Fr> tr(rounds), tri(rounds); for (size_t i = 0; i < rounds; ++i) { tr[i] = trf[rounds - 1 - i]; tri[i] = inv(tr[i]); }
-    const G2J ka = load_jac<Fp2>(final_ck_a), oa = load_jac<Fp2>(opening_a); const G1J kb = load_jac<Fp>(final_ck_b), ob = load_jac<Fp>(opening_b);
-    const G2A kaa = to_affine(ka); const G1A kba = to_affine(kb);
-    const Fr c = fs::kzg_challenge(tr[0], kaa, &kba);                                                                        // mod.rs:257-272
-    bool ok_a = false, ok_b = false; int32_t rc;
-    if ((rc = kzg_verify_g2(e, v, ka, oa, tri, inv(load_fr(r_shift)), c, &ok_a))) return rc;                                 // mod.rs:274-281
-    if ((rc = kzg_verify_g1(e, v, kb, ob, tr, Fr::one(), c, &ok_b))) return rc;                                              // mod.rs:282-289
-    const G1A a = to_affine(load_jac<Fp>(base_a)); const Fr b = load_fr(base_b);
+    G2A kaa; G1A kba; bool ok = false; int32_t rc;
+    if ((rc = tipa_verify_tail(e, v_srs, trf, final_ck_a, final_ck_b, opening_a, opening_b, r_shift, kaa, kba, &ok))) return rc;   // mod.rs:252-289
+    const G1A a = load_g1a(base_a); const Fr b = load_fr(base_b);
     Fp12 e1; if ((rc = pairing_host_pts(e, {a}, {kaa}, &e1))) return rc;                                                     // mod.rs:291-298
-    *accept = (ok_a && ok_b && e1 == ca && eq(smul_host(kba, b), cb) && eq(smul_host(a, b), ct)) ? 1 : 0;
+    *accept = (ok && e1 == ca && eq(smul_host(kba, b), cb) && eq(smul_host(a, b), ct)) ? 1 : 0;
     return RIPP_OK;
 }

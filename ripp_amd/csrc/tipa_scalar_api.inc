@@ -12,11 +12,7 @@ extern "C++" {
 struct ScalVecs {
     DevBuf MA, MA2, MB, MB2, KA, KA2, KB, KB2, jac1, jac2, qt2, part, out2, out1;
     FoldPre pKA, pKB;                       // second fold bases of the small rounds
-#define RIPP_SCAL_BUFS {&MA, &MA2, &MB, &MB2, &KA, &KA2, &KB, &KB2, &jac1, &jac2, &qt2, &part, &out2, &out1, &pKA.pow_h, &pKA.parts, &pKB.pow_h, &pKB.parts}
-    ScalVecs() { g_scal_cache.adopt(RIPP_SCAL_BUFS); }
-    ~ScalVecs() { g_scal_cache.park(RIPP_SCAL_BUFS); }
-    ScalVecs(const ScalVecs&) = delete; ScalVecs& operator=(const ScalVecs&) = delete;
-#undef RIPP_SCAL_BUFS
+    VecLease lease{&g_scal_cache, {&MA, &MA2, &MB, &MB2, &KA, &KA2, &KB, &KB2, &jac1, &jac2, &qt2, &part, &out2, &out1, &pKA.pow_h, &pKA.parts, &pKB.pow_h, &pKB.parts}};      // (last member)
     int32_t reserve(size_t n) {
         int32_t rc;
         for (DevBuf* b : {&MA, &MA2, &MB, &MB2}) if ((rc = b->reserve(n * sizeof(Fr)))) return rc;
@@ -34,7 +30,7 @@ static int32_t tipa_scalar_rounds(Engine* e, ScalVecs& v, size_t n, ripp_g2j* co
     int32_t rc;
     size_t len = n, round = 0;
     Fr prev_c = Fr::zero();
-    std::vector<Fr> part(2 * 1024);
+    FrDot2 dot;
     while (len > 1) {
         const size_t h = len / 2;
         const Fr* MA = v.MA.as<Fr>(); const Fr* MB = v.MB.as<Fr>(); const G2A* KA = v.KA.as<G2A>(); const G1A* KB = v.KB.as<G1A>();
@@ -56,10 +52,7 @@ static int32_t tipa_scalar_rounds(Engine* e, ScalVecs& v, size_t n, ripp_g2j* co
             if ((rc = e->msm_launch<Fp>(e->msm_scratch[1], e->stream3, KB + h, MB, h))) return rc;
             HIPCHK(hipMemcpyAsync(out1 + 1, e->msm_scratch[1].out.p, sizeof(G1J), hipMemcpyDeviceToDevice, e->stream3));
         }
-        const unsigned blocks = std::min<unsigned>(1024, nblk(h, 256));
-        hipLaunchKernelGGL(k_fr_dot2, dim3(blocks, 2), dim3(256), 0, e->stream, MA, MB, (uint32_t)h, v.part.as<Fr>());          // <m_a[h:], m_b[:h]>, <m_a[:h], m_b[h:]>
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(part.data(), v.part.p, 2 * blocks * sizeof(Fr), hipMemcpyDeviceToHost, e->stream));
+        if ((rc = dot.launch(e, MA, MB, h, v.part))) return rc;                                    // <m_a[h:], m_b[:h]>, <m_a[:h], m_b[h:]>
         if (!cross) { HIPCHK(hipStreamSynchronize(e->stream2)); HIPCHK(hipStreamSynchronize(e->stream3)); }
         G2J c2[2]; G1J c1[2];
         HIPCHK(hipMemcpyAsync(c2, out2, sizeof c2, hipMemcpyDeviceToHost, e->stream)); HIPCHK(hipMemcpyAsync(c1, out1, sizeof c1, hipMemcpyDeviceToHost, e->stream));
@@ -69,16 +62,14 @@ static int32_t tipa_scalar_rounds(Engine* e, ScalVecs& v, size_t n, ripp_g2j* co
         if ((rc = fold_precompute<Fp2>(e, e->stream, KA + h, h, v.pKA)) || (rc = fold_precompute<Fp>(e, e->stream2, KB + h, h, v.pKB))) return rc;
         e->stats.miller_products_ms += now_ms() - tp;                                             // (no Miller loop here: the round's commitments and inner products)
         const double th = now_ms();
-        Fr ip[2] = {Fr::zero(), Fr::zero()};
-        for (unsigned k = 0; k < blocks; ++k) { ip[0] = add(ip[0], part[k]); ip[1] = add(ip[1], part[blocks + k]); }
-        const G2A c2a[2] = {to_affine(c2[0]), to_affine(c2[1])}; const G1A c1a[2] = {to_affine(c1[0]), to_affine(c1[1])};
-        Fr c_inv; const Fr c = fs::gipa_scalar_challenge(round ? &prev_c : nullptr, c2a, c1a, ip, c_inv);
+        Fr ip[2]; dot.sum(ip);
+        Fr c_inv; const Fr c = fs::gipa_challenge(round ? &prev_c : nullptr, fs::Com{to_affine(c2[0]), to_affine(c1[0]), ip[0]}, fs::Com{to_affine(c2[1]), to_affine(c1[1]), ip[1]}, c_inv);
         e->stats.host_ms += now_ms() - th;
         std::memcpy(&com_g2[2 * round], c2, sizeof c2); std::memcpy(&com_g1[2 * round], c1, sizeof c1); std::memcpy(&com_fr[2 * round], ip, sizeof ip);
         std::memcpy(&transcript[round], &c, sizeof c);
         prev_c = c;
         const double tf = now_ms();
-        rc = folds_with_vm_fallback(e, h, [&]() -> int32_t {
+        rc = fork_join_folds(e, [&]() -> int32_t {
             int32_t r2;
             if ((r2 = fold_dev<Fp>(e, e->stream2, KB + h, KB, h, c, v.jac1, v.qt2, v.KB2.as<G1A>(), &v.pKB))) return r2;                 // ck_b <- ck_b_1 * c + ck_b_2   (ck_b_1 = ck_b[h:])
             hipLaunchKernelGGL(k_fold_fr2, dim3(nblk(h, 256), 2), dim3(256), 0, e->stream3, MA, MB, (uint32_t)h, c, c_inv, v.MA2.as<Fr>(), v.MB2.as<Fr>());   // m_a <- m_a_1 * c + m_a_2, m_b <- m_b_2 * c_inv + m_b_1
@@ -97,19 +88,8 @@ static int32_t tipa_scalar_rounds(Engine* e, ScalVecs& v, size_t n, ripp_g2j* co
 
 // _compute_recursive_challenges (gipa.rs:322-363) for this instantiation: folds the steps into (ca, cb, ct) = (com_a, com_b, com_t); tr in ROUND order
 static void tipa_scalar_replay(G2J& ca, G1J& cb, Fr& ct, const ripp_g2j* com_g2, const ripp_g1j* com_g1, const ripp_fr* com_fr, size_t rounds, std::vector<Fr>& tr) {
-    tr.resize(rounds);
-    for (size_t k = 0; k < rounds; ++k) {
-        const G2A g2[2] = {to_affine(load_jac<Fp2>(&com_g2[2 * k])), to_affine(load_jac<Fp2>(&com_g2[2 * k + 1]))};
-        const G1A g1[2] = {to_affine(load_jac<Fp>(&com_g1[2 * k])), to_affine(load_jac<Fp>(&com_g1[2 * k + 1]))};
-        const Fr ip[2] = {load_fr(&com_fr[2 * k]), load_fr(&com_fr[2 * k + 1])};
-        Fr c_inv; const Fr c = fs::gipa_scalar_challenge(k ? &tr[k - 1] : nullptr, g2, g1, ip, c_inv);
-        auto f2 = host_pool().submit([&g2, c_inv]() { return smul_host(g2[1], c_inv); });
-        auto f1 = host_pool().submit([&g1, c, c_inv]() { return add(smul_host(g1[0], c), smul_host(g1[1], c_inv)); });
-        ca = add(add(ca, smul_host(g2[0], c)), f2.get());                                                                 // com + com_1 * c + com_2 * c_inv   (gipa.rs:358-360)
-        cb = add(cb, f1.get());
-        ct = add(add(ct, mul(ip[0], c)), mul(ip[1], c_inv));
-        tr[k] = c;
-    }
+    gipa_replay<G2A, G1A, Fr>(ca, cb, ct, rounds, tr, [&](size_t k, auto& s1, auto& s2) {                                     // (no GT member: nothing to reject)
+        s1 = {load_g2a(&com_g2[2 * k]), load_g1a(&com_g1[2 * k]), load_fr(&com_fr[2 * k])}; s2 = {load_g2a(&com_g2[2 * k + 1]), load_g1a(&com_g1[2 * k + 1]), load_fr(&com_fr[2 * k + 1])}; });
 }
 }  // extern "C++"
 
@@ -145,18 +125,12 @@ API int32_t ripp_tipa_scalar_verify(const ripp_verifier_srs* v_srs, const ripp_g
     if (!v_srs || !com_a || !com_b || !com_t || !com_g2 || !com_g1 || !com_fr || !base_a || !base_b || !final_ck_a || !final_ck_b || !opening_a || !opening_b ||
         !r_shift || !accept || rounds == 0 || rounds > 24) return RIPP_ERR_ARG;
     LOCK; ENGINE;
-    const VSrs v = load_vsrs(v_srs);
     G2J ca = load_jac<Fp2>(com_a); G1J cb = load_jac<Fp>(com_b); Fr ct = load_fr(com_t);
     std::vector<Fr> trf;
     tipa_scalar_replay(ca, cb, ct, com_g2, com_g1, com_fr, rounds, trf);                                                     // mod.rs:249-251
-    std::vector<Fr> tr(rounds), tri(rounds); for (size_t i = 0; i < rounds; ++i) { tr[i] = trf[rounds - 1 - i]; tri[i] = inv(tr[i]); }
-    const G2J ka = load_jac<Fp2>(final_ck_a), oa = load_jac<Fp2>(opening_a); const G1J kb = load_jac<Fp>(final_ck_b), ob = load_jac<Fp>(opening_b);
-    const G2A kaa = to_affine(ka); const G1A kba = to_affine(kb);
-    const Fr c = fs::kzg_challenge(tr[0], kaa, &kba);                                                                        // mod.rs:257-272
-    bool ok_a = false, ok_b = false; int32_t rc;
-    if ((rc = kzg_verify_g2(e, v, ka, oa, tri, inv(load_fr(r_shift)), c, &ok_a))) return rc;                                 // mod.rs:274-281
-    if ((rc = kzg_verify_g1(e, v, kb, ob, tr, Fr::one(), c, &ok_b))) return rc;                                              // mod.rs:282-289
+    G2A kaa; G1A kba; bool ok = false; int32_t rc;
+    if ((rc = tipa_verify_tail(e, v_srs, trf, final_ck_a, final_ck_b, opening_a, opening_b, r_shift, kaa, kba, &ok))) return rc;   // mod.rs:252-289
     const Fr a = load_fr(base_a), b = load_fr(base_b);                                                                       // mod.rs:291-298
-    *accept = (ok_a && ok_b && eq(smul_host(kaa, a), ca) && eq(smul_host(kba, b), cb) && mul(a, b) == ct) ? 1 : 0;
+    *accept = (ok && eq(smul_host(kaa, a), ca) && eq(smul_host(kba, b), cb) && mul(a, b) == ct) ? 1 : 0;
     return RIPP_OK;
 }

@@ -91,6 +91,23 @@ static int32_t tpc_reserve_first(Engine* e, size_t n) {
     return RIPP_OK;
 }
 
+// Both inner products of a scalar round, <a[h:], b[:h]> and <a[:h], b[h:]>: launch() enqueues k_fr_dot2 on the engine's stream (one partial per block and product
+// into dpart, 2 * 1024 Fr) and the copy of the partials behind it; sum() adds them up once that stream has been synchronised.
+struct FrDot2 {
+    std::vector<Fr> part = std::vector<Fr>(2 * 1024); unsigned blocks = 0;
+    int32_t launch(Engine* e, const Fr* a, const Fr* b, size_t h, DevBuf& dpart) {
+        blocks = std::min<unsigned>(1024, nblk(h, 256));
+        hipLaunchKernelGGL(k_fr_dot2, dim3(blocks, 2), dim3(256), 0, e->stream, a, b, (uint32_t)h, dpart.as<Fr>());
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(part.data(), dpart.p, 2 * blocks * sizeof(Fr), hipMemcpyDeviceToHost, e->stream));
+        return RIPP_OK;
+    }
+    void sum(Fr ip[2]) const {
+        ip[0] = ip[1] = Fr::zero();
+        for (unsigned k = 0; k < blocks; ++k) { ip[0] = add(ip[0], part[k]); ip[1] = add(ip[1], part[blocks + k]); }
+    }
+};
+
 // GIPA<ScalarInnerProduct, PedersenCommitment<G1>, SSMPlaceholder, IdentityCommitment<Fr>>::_prove (gipa.rs:181-312) on e->tpc_m (message), e->tpc_b
 // (structured scalars) and e->tpc_k (keys), n elements each, filled on e->stream by the caller (tpc_reserve_first).  ext0 (optional): the extended form
 // of the n keys as they stand before the first round (a resident ripp_tpc_ck has it); after every key fold the batch pipeline rebuilds its own.
@@ -101,7 +118,7 @@ static int32_t tpc_scalar_rounds(Engine* e, size_t n, const QAff<Fp>* ext0, ripp
     int32_t rc; if ((rc = e->sync())) return rc;
     size_t len = n, round = 0; Fr prev_c = Fr::zero();
     g_tpc_round_ms.clear();
-    std::vector<Fr> part(2 * 1024);
+    FrDot2 dot;
     while (len > 1) {
         const size_t h = len / 2;
         const Fr* M = e->tpc_m.as<Fr>(); const Fr* B = e->tpc_b.as<Fr>(); const G1A* K = e->tpc_k.as<G1A>();
@@ -114,11 +131,7 @@ static int32_t tpc_scalar_rounds(Engine* e, size_t n, const QAff<Fp>* ext0, ripp
         } else {
             if ((rc = e->msm_launch<Fp>(e->msm_scratch[0], e->stream2, K, M + h, h)) || (rc = e->msm_launch<Fp>(e->msm_scratch[1], e->stream3, K + h, M, h))) return rc;
         }
-        const unsigned blocks = std::min<unsigned>(1024, nblk(h, 256));
-        hipLaunchKernelGGL(k_fr_dot2, dim3(blocks, 2), dim3(256), 0, e->stream, M, B, (uint32_t)h, e->tpc_part.as<Fr>());      // <m[h:], b[:h]>, <m[:h], b[h:]>
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(part.data(), e->tpc_part.p, 2 * blocks * sizeof(Fr), hipMemcpyDeviceToHost, e->stream));
-        if ((rc = e->sync())) return rc;
+        if ((rc = dot.launch(e, M, B, h, e->tpc_part)) || (rc = e->sync())) return rc;                                       // <m[h:], b[:h]>, <m[:h], b[h:]>
         if (!cross) {
             HIPCHK(hipStreamSynchronize(e->stream2)); HIPCHK(hipStreamSynchronize(e->stream3));
             cm[0] = *reinterpret_cast<const G1J*>(e->msm_scratch[0].host_out); cm[1] = *reinterpret_cast<const G1J*>(e->msm_scratch[1].host_out);
@@ -126,15 +139,13 @@ static int32_t tpc_scalar_rounds(Engine* e, size_t n, const QAff<Fp>* ext0, ripp
         g_tpc_round_ms.push_back(now_ms() - tp);
         if ((rc = fold_precompute<Fp>(e, e->stream2, K + h, h, g_tpc_pre))) return rc;        // small rounds: during the host phase
         const double th = now_ms();                                                        // (no Miller loop in this tier: stats.miller_products_ms stays 0, the commitments are total_ms less fold_ms and host_ms)
-        Fr ip[2] = {Fr::zero(), Fr::zero()};
-        for (unsigned k = 0; k < blocks; ++k) { ip[0] = add(ip[0], part[k]); ip[1] = add(ip[1], part[blocks + k]); }
-        const G1A cma[2] = {to_affine(cm[0]), to_affine(cm[1])};
-        Fr c_inv; const Fr c = fs::gipa_scalar_ssm_challenge(round ? &prev_c : nullptr, cma, ip, c_inv);
+        Fr ip[2]; dot.sum(ip);
+        Fr c_inv; const Fr c = fs::gipa_challenge(round ? &prev_c : nullptr, fs::Com{to_affine(cm[0]), fs::SSMPlaceholder{}, ip[0]}, fs::Com{to_affine(cm[1]), fs::SSMPlaceholder{}, ip[1]}, c_inv);
         e->stats.host_ms += now_ms() - th;
         std::memcpy(&com_g1[2 * round], cm, sizeof cm); std::memcpy(&com_fr[2 * round], ip, sizeof ip); std::memcpy(&transcript[round], &c, sizeof c);
         prev_c = c;
         const double tf = now_ms();
-        rc = folds_with_vm_fallback(e, h, [&]() -> int32_t {
+        rc = fork_join_folds(e, [&]() -> int32_t {
             int32_t r2;
             if ((r2 = fold_dev<Fp>(e, e->stream2, K + h, K, h, c_inv, e->tpc_jac, e->qtab, e->tpc_k2.as<G1A>(), &g_tpc_pre))) return r2;       // ck <- ck_2 * c_inv + ck_1
             hipLaunchKernelGGL(k_fold_fr2, dim3(nblk(h, 256), 2), dim3(256), 0, e->stream3, M, B, (uint32_t)h, c, c_inv, e->tpc_m2.as<Fr>(), e->tpc_b2.as<Fr>());   // m <- m_1 * c + m_2, b <- b_2 * c_inv + b_1
@@ -161,17 +172,10 @@ template <class F> static int32_t tpc_final_key(Engine* e, const Affine<F>* dkey
 // com = (com_a: the Pedersen commitment, com_t: the inner product).
 static int32_t tpc_scalar_verify_core(Engine* e, const G1A* dkeys, size_t rounds, const G1J& com_a, const Fr& com_t, const Fr& scalar_b,
                                       const ripp_g1j* com_g1, const ripp_fr* com_fr, const Fr& base_a, const Fr& base_b, bool* ok) {
-    G1J ca = com_a; Fr ct = com_t;
-    std::vector<Fr> tr(rounds);
-    for (size_t k = 0; k < rounds; ++k) {                                                                                // gipa.rs:329-360
-        const G1A g1[2] = {to_affine(load_jac<Fp>(&com_g1[2 * k])), to_affine(load_jac<Fp>(&com_g1[2 * k + 1]))};
-        const Fr ip[2] = {load_fr(&com_fr[2 * k]), load_fr(&com_fr[2 * k + 1])};
-        Fr c_inv; const Fr c = fs::gipa_scalar_ssm_challenge(k ? &tr[k - 1] : nullptr, g1, ip, c_inv);
-        auto f = host_pool().submit([&g1, c_inv]() { return smul_host(g1[1], c_inv); });
-        ca = add(add(smul_host(g1[0], c), ca), f.get());
-        ct = add(add(mul(ip[0], c), ct), mul(ip[1], c_inv));
-        tr[k] = c;
-    }
+    G1J ca = com_a; Fr ct = com_t; fs::SSMPlaceholder cb;
+    std::vector<Fr> tr;
+    gipa_replay<G1A, fs::SSMPlaceholder, Fr>(ca, cb, ct, rounds, tr, [&](size_t k, auto& s1, auto& s2) {                 // gipa.rs:329-360 (no GT member: nothing to reject)
+        s1 = {load_g1a(&com_g1[2 * k]), {}, load_fr(&com_fr[2 * k])}; s2 = {load_g1a(&com_g1[2 * k + 1]), {}, load_fr(&com_fr[2 * k + 1])}; });
     G1J ka; int32_t rc;
     if ((rc = tpc_final_key<Fp>(e, dkeys, final_key_exponents(tr, true), &ka))) return rc;
     // gipa_valid (:100-106, gipa.rs:401-415): the Pedersen commitment of a_base under the final key, the (empty) placeholder commitment, the product with the

@@ -140,9 +140,9 @@ API int32_t ripp_vec_fold(const ripp_vec* hi, const ripp_vec* lo, const ripp_fr*
                 if (!(rc = e->normalize_dev<Fp2>(e->jacG2.as<G2J>(), half, vec_ptr<G2A>(v)))) rc = e->sync();
             }
         } else if (hi->kind == RIPP_VEC_G1) {
-            rc = folds_with_vm_fallback(e, half, [&]() { return fold_dev<Fp>(e, e->stream, vec_ptr<G1A>(hi), vec_ptr<G1A>(lo), half, sm, e->jacG1, e->qtab, vec_ptr<G1A>(v)); });
+            rc = fork_join_folds(e, [&]() { return fold_dev<Fp>(e, e->stream, vec_ptr<G1A>(hi), vec_ptr<G1A>(lo), half, sm, e->jacG1, e->qtab, vec_ptr<G1A>(v)); });
         } else {
-            rc = folds_with_vm_fallback(e, half, [&]() { return fold_dev<Fp2>(e, e->stream, vec_ptr<G2A>(hi), vec_ptr<G2A>(lo), half, sm, e->jacG2, e->qtab, vec_ptr<G2A>(v)); });
+            rc = fork_join_folds(e, [&]() { return fold_dev<Fp2>(e, e->stream, vec_ptr<G2A>(hi), vec_ptr<G2A>(lo), half, sm, e->jacG2, e->qtab, vec_ptr<G2A>(v)); });
         }
         if (rc) { vec_drop(v); return rc; }
     }
