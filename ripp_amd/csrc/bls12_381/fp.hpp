@@ -41,6 +41,13 @@
 
 namespace ripp {
 
+// |x| of the BLS12 parameter x (the Miller loop's and the final exponentiation's exponent, the base u of the GLS digits)
+#if defined(RIPP_BLS12_377)
+constexpr uint64_t BLS_X_ABS = 0x8508c00000000001ull;   // x > 0
+#else
+constexpr uint64_t BLS_X_ABS = 0xd201000000010000ull;   // |x|, x < 0
+#endif
+
 // ---------------------------------------------------------------- limb helpers
 RIPP_HD uint32_t addc32(uint32_t a, uint32_t b, uint32_t& carry) {
     uint32_t co;

@@ -16,12 +16,10 @@
 namespace ripp {
 
 #if defined(RIPP_BLS12_377)
-constexpr uint64_t BLS_X_ABS = 0x8508c00000000001ull;   // x > 0 (no conjugations)
-constexpr bool BLS_X_NEG = false;
+constexpr bool BLS_X_NEG = false;                        // x > 0 (no conjugations); |x| = BLS_X_ABS (fp.hpp)
 constexpr int N_LINES = 69;                              // 63 doubling + 6 addition steps
 #else
-constexpr uint64_t BLS_X_ABS = 0xd201000000010000ull;   // |x|, x < 0
-constexpr bool BLS_X_NEG = true;
+constexpr bool BLS_X_NEG = true;                         // x < 0
 constexpr int N_LINES = 68;                              // 63 doubling + 5 addition steps
 #endif
 

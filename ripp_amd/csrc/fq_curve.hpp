@@ -7,6 +7,7 @@
 #pragma once
 #include "fq28.hpp"
 #include "kernels.hpp"
+#include "recode.hpp"     // WnafG1x4
 
 namespace ripp {
 
@@ -245,7 +246,6 @@ __global__ void __launch_bounds__(256, 2) k_fold_g1_tab_q(const G1A* __restrict_
 // i.e. SIXTEEN 32-bit strings over the same kind of table the round-0 fold uses (bases 2^(32 b) P, odd multiples), now built over A1 | A2 | A3:
 // 33 doublings + ~16 x 6.4 additions per output where the two folds take 2 x (33 + ~26) for round 0 and 128 + ~43 for round 1.
 // String 4 u + b = 32-bit word b of scalar u:  u = 0: x0 on A2 (table element q + i)   1: k1 on A3 (2 q + i)   2: k2 on phi(A3)   3: x1 on A1 (i).
-struct WnafG1x4 { int8_t d[16][36]; int len; };
 __device__ __noinline__ inline G1J fold_g1_fused_complete(const G1A* __restrict__ tab, size_t tstride, int M, const G1A& l, uint32_t q, uint32_t i, const WnafG1x4& dg) {
     G1J a2 = jac_inf<Fp>();
 #pragma unroll 1

@@ -7,6 +7,7 @@
 // (588 + 392 multiply-adds against 392 + 392: the (a0 + a1)(a0 - a1) trick needs u^2 = -1).
 #pragma once
 #include "fq_curve.hpp"
+#include "recode.hpp"     // Wnaf16x3
 
 namespace ripp {
 
@@ -246,7 +247,6 @@ __global__ void __launch_bounds__(64) k_fold_g2_tab_fix(const uint4* __restrict_
 // stays x-scaled).  Three digit sets over the round-0 kind of table (rows (4 b + j) M + m = psi^j((2 m + 1) 2^(16 b) Q)), built over B0 | B1 | B2:
 // set 0: x0 x1 (full width: four GLS digits) on B0 (element i), set 1: x0 on B1 (q + i), set 2: x1 on B2 (2 q + i) -- 17 doublings + ~32 x 3.2
 // additions per output where the two folds take 2 x (17 + ~45) for round 0 and 65 + ~52 plus its in-round tables for round 1.
-struct Wnaf16x3 { Wnaf16 s[3]; int len; };
 __device__ __noinline__ inline void fold_g2_fused_complete(const uint4* __restrict__ qtab, size_t stride, int M, const G2A* __restrict__ lo, uint32_t q, uint32_t i, const Wnaf16x3& dg, G2J* __restrict__ out) {
     G2J acc = jac_inf<Fp2>();
 #pragma unroll 1

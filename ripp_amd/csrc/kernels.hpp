@@ -14,6 +14,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "bls12_381/pairing.hpp"
+#include "recode.hpp"     // the digit structs the fold kernels take by value (ScalarBits, NafDigits, GlvDigits, GlsDigits, ...)
 
 namespace ripp {
 
@@ -25,8 +26,6 @@ namespace ripp {
 #endif
 constexpr int LINE_CHUNKS = 18;    // 3 Fp2 = 72 dwords
 constexpr int FP12_CHUNKS = 36;    // 144 dwords
-
-struct ScalarBits { uint32_t w[8]; int nbits; };   // canonical little-endian scalar shared by all lanes of a launch
 
 // ---- chunked SoA accessors -------------------------------------------------------------------------------
 template <int NCH, class T>
@@ -271,7 +270,6 @@ __global__ void __launch_bounds__(256) k_fold_jac(const Jac<F>* __restrict__ hi,
 // s = d0 + d1 u + d2 u^2 + d3 u^3 (0 <= d_j < u), each d_j NAF-recoded, and every lane runs the SAME joint
 // double-and-add over <= 65 digit positions: 65 doublings + ~87 mixed additions instead of 255 + ~128.
 // The four affine points [u^j]Q of a lane are parked in HBM (chunked SoA, L2-resident) so only T stays in VGPRs.
-struct GlsDigits { int8_t d[4][68]; int len; };
 constexpr int G2A_CHUNKS = 12;     // 192 B
 
 RIPP_HD G2A gls_image(const G2A& q, int j) {
@@ -360,7 +358,6 @@ __global__ void __launch_bounds__(64) k_fold_g2_combine8(const G2J* __restrict__
 }
 
 // Single-scalar NAF fold (G1 with the 128-bit SIPP challenge): out[i] = s*hi[i] + lo[i]
-struct NafDigits { int8_t d[260]; int len; };
 template <class F>
 __global__ void __launch_bounds__(256) k_fold_affine_naf(const Affine<F>* __restrict__ hi, const Affine<F>* __restrict__ lo, uint32_t half,
                                                           NafDigits dg, Jac<F>* __restrict__ out) {
@@ -381,7 +378,6 @@ __global__ void __launch_bounds__(256) k_fold_affine_naf(const Affine<F>* __rest
 // phi(x, y) = (beta x, y) = [lambda](x, y), lambda = u^2 - 1 ~ sqrt(r):  s = s1 + s2 lambda with s1, s2 <= 128 bits, so
 //   out[i] = s1 * P + s2 * phi(P) + lo[i]
 // costs 128 doublings + ~86 additions instead of 255 + ~85.  d1 / d2: NAF digit strings of s1 / s2 (shared by the launch).
-struct GlvDigits { int8_t d1[132]; int8_t d2[132]; int len; };
 __global__ void __launch_bounds__(256) k_fold_g1_glv(const G1A* __restrict__ hi, const G1A* __restrict__ lo, uint32_t half, GlvDigits dg, G1J* __restrict__ out) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= half) return;
@@ -431,7 +427,6 @@ __global__ void __launch_bounds__(256) k_fold_g1_two(const G1A* __restrict__ hi,
 }
 // G2: every base-u digit of the GLS decomposition is split at bit 32: eight digit strings of <= 33 NAF digits over the eight bases
 // psi^j(Q), psi^j(2^32 Q) (psi commutes with doubling): 33 doublings + ~88 additions instead of 65 + ~87.
-struct Gls8Digits { int8_t d[8][36]; int len; };
 __global__ void __launch_bounds__(64, RIPP_OCC) k_fold_g2_gls8(const G2A* __restrict__ hi, const G2A* __restrict__ hi2, const G2A* __restrict__ lo, uint32_t half,
                                                       Gls8Digits dg, uint4* __restrict__ qtab, size_t stride, G2J* __restrict__ out) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -464,10 +459,7 @@ __global__ void __launch_bounds__(64, RIPP_OCC) k_fold_g2_gls8(const G2A* __rest
 // width-w wNAF strings of 32 (G1) / 16 (G2) bits -- one addition per w + 1 digit positions instead of one per 3, and half the doublings
 // again.  w = 5: G1 33 doublings + ~22 additions (two-base NAF form: 65 + ~43); G2: 17 doublings + ~45 additions (33 + ~88).
 // Same group elements, hence the same proof bytes.
-#ifndef RIPP_FOLD_W
-#define RIPP_FOLD_W 5                                   // wNAF width of the table folds
-#endif
-constexpr int FOLD_TAB_M = 1 << (RIPP_FOLD_W - 2);      // odd multiples 1, 3, .., 2 M - 1 per base
+// (RIPP_FOLD_W, FOLD_TAB_M and the digit structs Wnaf4 / Wnaf16: recode.hpp)
 template <class F>
 __global__ void __launch_bounds__(64, 2) k_odd_multiples(const Affine<F>* __restrict__ base, uint32_t n, int M, Jac<F>* __restrict__ out) {   // out[m][i] = (2m + 3) base[i], m < M - 1
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -480,8 +472,6 @@ __global__ void __launch_bounds__(64, 2) k_odd_multiples(const Affine<F>* __rest
     for (int m = 1; m < M - 1; ++m) { t = add(t, b2); out[(size_t)m * n + i] = t; }
 }
 // Four bases per element (G1: 2^(32 b) hi[i], G2: 2^(16 b) hi[i], b < 4), so the chain has 32 / 16 doublings.
-struct Wnaf4 { int8_t d[4][36]; int len; };            // G1: string b = 32-bit word b of the 128-bit challenge
-struct Wnaf16 { int8_t d[16][20]; int len; };          // G2: string 4 b + j = 16-bit piece b of GLS digit j
 // tab[e][i], e = M b + m: (2m + 1) * (base b of element i)
 __global__ void __launch_bounds__(256) k_fold_g1_tab(const G1A* __restrict__ tab, size_t tstride, int M, const G1A* __restrict__ lo, uint32_t half, Wnaf4 dg, G1J* __restrict__ out) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;

@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 #include "bls12_381/pairing.hpp"
 #include "kernels.hpp"
+#include "recode.hpp"     // GlsDigits2
 #include "fq28.hpp"
 
 namespace ripp {
@@ -436,7 +437,6 @@ __global__ void __launch_bounds__(256) k_vm_fold_g2_joint(const G2A* __restrict_
 
 // The same joint walk over TWO bases with a full-width scalar each: out[i] = s1 * p1[i] + s2 * p2[i] (8 GLS digit strings; lanes 0..3 keep the
 // images of p1[i], lanes 4..7 those of p2[i]).  This is the fold that returns an x-scaled G2 vector to the plain one (engine.hip job_fold).
-struct GlsDigits2 { GlsDigits a, b; };
 __global__ void __launch_bounds__(256) k_vm_fold_g2_joint2(const G2A* __restrict__ p1, const G2A* __restrict__ p2, uint32_t half, GlsDigits2 dg, G2J* __restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) unsigned char vm_smem[];
     VmSlot* const lds = reinterpret_cast<VmSlot*>(vm_smem);

@@ -8,10 +8,9 @@
 #pragma once
 #include "msm.hpp"      // VmCurve<F>
 #include "scale.hpp"    // scale_bias / scale_digit
+#include "recode.hpp"   // SplitDigits
 
 namespace ripp {
-
-struct SplitDigits { int8_t d[8][68]; int len; };     // NAF digit strings; G1: d[0] = low half, d[1] = high half; G2: d[j] low, d[4+j] high of GLS digit j
 
 // image t of a base: G1: t = 1 is the GLV endomorphism phi(x, y) = (beta x, y) (full-width GIPA scalars); G2: psi^t (GLS)
 __device__ __forceinline__ Jac<Fp> vm_image_h(const Jac<Fp>& p, int t) { return t == 0 ? p : Jac<Fp>{fmul(p.x, fp_const(RIPP_GLV_BETA)), p.y, p.z}; }

@@ -42,15 +42,19 @@ def test_vec_round_trip_views_and_inner_products(engine, orc, n):
 
 @pytest.mark.parametrize("n", [2, 16, 512, 1 << 13, 1 << 16])
 def test_vec_folds(engine, orc, n):
-    """out[i] = s hi[i] + lo[i] on resident halves = ripp_fold_* on host slices (every size class: VM, split, GLS, table kernels)"""
+    """out[i] = s hi[i] + lo[i] on resident halves = ripp_fold_* on host slices (every size class: VM, split, GLS, table kernels) = the CPU oracle's fold (n <= 2^13)"""
     a, b, r = orc.blind_g1(orc.gen_g1(70, n), 5), orc.blind_g2(orc.gen_g2(90, n), 6), orc.gen_scalars(8, n)
     c = orc.fr_array([0x1234567890ABCDEF0FEDCBA098765432 << 64 | 0x1111])[0]
     c128 = orc.fr_array([0xFEDCBA9876543210FEDCBA9876543210])[0]
     s = n // 2
     va, vb, vr = engine.Vec.upload("G1", a), engine.Vec.upload("G2", b), engine.Vec.upload("Fr", r)
+    if n <= 1 << 13: a_aff, b_aff = orc.normalize_g1(a), orc.normalize_g2(b)
     for sc in (c, c128):
-        assert np.array_equal(va[s:].fold(va[:s], sc).download(), _aff1(engine, engine.fold_g1(a[s:], a[:s], sc)))
-        assert np.array_equal(vb[s:].fold(vb[:s], sc).download(), _aff2(engine, engine.fold_g2(b[s:], b[:s], sc)))
+        f1, f2 = va[s:].fold(va[:s], sc).download(), vb[s:].fold(vb[:s], sc).download()
+        assert np.array_equal(f1, _aff1(engine, engine.fold_g1(a[s:], a[:s], sc)))
+        assert np.array_equal(f2, _aff2(engine, engine.fold_g2(b[s:], b[:s], sc)))
+        if n <= 1 << 13:                                                                        # ... and = the oracle's plain double-and-add fold of the same elements
+            assert np.array_equal(f1, orc.fold_g1_a(a_aff[s:], a_aff[:s], sc)) and np.array_equal(f2, orc.fold_g2_a(b_aff[s:], b_aff[:s], sc))
     import ripp_amd.gipa as G
     assert np.array_equal(vr[s:].fold(vr[:s], c).download(), G.Fr.fold(r[s:], r[:s], c))
     # exceptional cases inside a fold: hi == lo (s = 1 doubles, s = -1 cancels), infinity in either operand
