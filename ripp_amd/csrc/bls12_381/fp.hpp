@@ -205,7 +205,7 @@ RIPP_HD Mont<P> mul_cios(const Mont<P>& a, const Mont<P>& b) {
     Mont<P> r;
 #pragma unroll
     for (int i = 0; i < N; ++i) r.l[i] = t[i];
-    reduce_once(r);                            // p < 2^(32N-2) for both fields => t < 2p
+    reduce_once(r);                            // t < 2p, and 2p < 2^(32N) for every field here (Fr of BLS12-381 by one spare bit, the others by two or more)
     return r;
 }
 

@@ -144,4 +144,17 @@ __global__ void __launch_bounds__(256) k_kzg_quotient(const Fr* __restrict__ p, 
     }
 }
 
+inline Fr fr_pow_u(Fr b, size_t k) { Fr r = Fr::one(); while (k) { if (k & 1) r = mul(r, b); b = mul(b, b); k >>= 1; } return r; }
+// The launch sequence of the scan (host): p = m >= 1 coefficients in device memory, h and cin = ceil(m / KZG_CHUNK) elements each, q = m + 1 elements
+// (q[0 .. m - 1) the quotient, q[m] = p(z); q[m - 1] is not written).  per_override = 0: the lane share of the formula; the device harness
+// (tests/device/fr_edges.hip) passes other shares, any per with per * KZG_SCAN_LANES >= nchunk is valid.
+inline void kzg_quotient_launch(hipStream_t stream, const Fr* p, size_t m, const Fr& z, Fr* h, Fr* cin, Fr* q, size_t per_override = 0) {
+    const size_t nchunk = (m + KZG_CHUNK - 1) / KZG_CHUNK, per = per_override ? per_override : (nchunk + KZG_SCAN_LANES - 1) / KZG_SCAN_LANES;
+    const Fr zT = fr_pow_u(z, KZG_CHUNK), zTper = fr_pow_u(zT, per);
+    const dim3 grid((unsigned)((nchunk + 255) / 256));
+    hipLaunchKernelGGL(k_kzg_chunk_sums, grid, dim3(256), 0, stream, p, (uint32_t)m, z, h);
+    hipLaunchKernelGGL(k_kzg_carry_scan, dim3(1), dim3(KZG_SCAN_LANES), 0, stream, h, (uint32_t)nchunk, (uint32_t)per, zT, zTper, cin);
+    hipLaunchKernelGGL(k_kzg_quotient, grid, dim3(256), 0, stream, p, (uint32_t)m, z, cin, q, q + m);
+}
+
 }  // namespace ripp

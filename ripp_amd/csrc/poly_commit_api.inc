@@ -175,14 +175,11 @@ static size_t pc_stripped_len(const ripp_fr* c, size_t len) {
 // quotient of p (m coefficients in device memory) by (X - z) into e->pc_q (m - 1 coefficients) and p(z): the suffix scan of msm_batch.hpp
 static int32_t kzg_quotient_dev(Engine* e, const Fr* dp, size_t m, const Fr& z, Fr* eval_host) {
     if (m == 0) { *eval_host = Fr::zero(); return RIPP_OK; }
-    const size_t nchunk = (m + KZG_CHUNK - 1) / KZG_CHUNK, per = (nchunk + KZG_SCAN_LANES - 1) / KZG_SCAN_LANES;
+    const size_t nchunk = (m + KZG_CHUNK - 1) / KZG_CHUNK;
     int32_t rc;
     if ((rc = e->pc_h.reserve(nchunk * sizeof(Fr))) || (rc = e->pc_cin.reserve(nchunk * sizeof(Fr))) || (rc = e->pc_q.reserve((m + 1) * sizeof(Fr)))) return rc;
-    const Fr zT = fr_pow_u(z, KZG_CHUNK), zTper = fr_pow_u(zT, per);
     Fr* const q = e->pc_q.as<Fr>();                                                    // q[0 .. m - 1), then one slot for p(z)
-    hipLaunchKernelGGL(k_kzg_chunk_sums, dim3(nblk(nchunk, 256)), dim3(256), 0, e->stream, dp, (uint32_t)m, z, e->pc_h.as<Fr>());
-    hipLaunchKernelGGL(k_kzg_carry_scan, dim3(1), dim3(KZG_SCAN_LANES), 0, e->stream, e->pc_h.as<Fr>(), (uint32_t)nchunk, (uint32_t)per, zT, zTper, e->pc_cin.as<Fr>());
-    hipLaunchKernelGGL(k_kzg_quotient, dim3(nblk(nchunk, 256)), dim3(256), 0, e->stream, dp, (uint32_t)m, z, e->pc_cin.as<Fr>(), q, q + m);
+    kzg_quotient_launch(e->stream, dp, m, z, e->pc_h.as<Fr>(), e->pc_cin.as<Fr>(), q);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(eval_host, q + m, sizeof(Fr), hipMemcpyDeviceToHost, e->stream));
     return e->sync();

@@ -230,7 +230,6 @@ template <class T> static int32_t shard_gather_tail(Engine* e, const ShardCtx& s
 static bool is_pow2(size_t v) { return v != 0 && !(v & (v - 1)); }
 static size_t log2_sz(size_t v) { size_t l = 0; while (((size_t)1 << l) < v) ++l; return l; }
 static std::vector<Fr> fr_powers(const Fr& s, size_t n) { std::vector<Fr> p(n); if (n) p[0] = Fr::one(); for (size_t i = 1; i < n; ++i) p[i] = mul(p[i - 1], s); return p; }      // structured_scalar_power
-static Fr fr_pow_u(Fr b, size_t k) { Fr r = Fr::one(); while (k) { if (k & 1) r = mul(r, b); b = mul(b, b); k >>= 1; } return r; }
 // the sqrt split of a univariate degree (poly_commit/mod.rs:299-306, transparent.rs:221-227): the skew factor is min(skew_cap, sqrt / 2); who / cite: the error text's
 static int32_t sqrt_split(size_t degree, size_t skew_cap, const char* who, const char* cite, size_t* x_degree, size_t* y_degree) {
     if (!x_degree || !y_degree || degree >= ((size_t)1 << 62)) return RIPP_ERR_ARG;

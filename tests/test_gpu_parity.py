@@ -181,18 +181,26 @@ def test_msm_sort_and_two_stream_forms_vs_oracle(engine, orc, n):
             for k in env: del os.environ[k]
 
 
-@pytest.mark.parametrize("n", [0, 1, 255, 256, 257, 100003])
+def _fr_ints(orc, limbs):
+    """(n, 4) Montgomery limbs -> integers, in one pass over the bytes"""
+    rinv = pow(1 << 256, -1, orc.R)
+    raw = np.ascontiguousarray(limbs, dtype=np.uint64).reshape(-1, 4).tobytes()
+    return [int.from_bytes(raw[o:o + 32], "little") * rinv % orc.R for o in range(0, len(raw), 32)]
+
+
+@pytest.mark.parametrize("n", [0, 1, 255, 256, 257, 100003, 262143, 262144, 262145, 524289])
 def test_scalar_inner_product(engine, orc, n):
-    """ScalarInnerProduct (inner_products/src/lib.rs:144-166) against Python integers; length mismatch raises as the other products do."""
+    """ScalarInnerProduct (inner_products/src/lib.rs:144-166) against Python integers at every n; length mismatch raises as the other products do.
+    The host caps k_fr_dot's grid at 1024 blocks of 256 lanes: from n = 262145 on a lane takes a second trip of its grid-stride loop."""
     l, r = orc.gen_scalars(5, n), orc.gen_scalars(6, n)
-    exp = sum(orc.limbs_to_fr(a) * orc.limbs_to_fr(b) for a, b in zip(l[:2000], r[:2000])) % orc.R if n <= 2000 else None
+    li, ri = _fr_ints(orc, l), _fr_ints(orc, r)
+    exp = sum(a * b for a, b in zip(li, ri)) % orc.R
     got = orc.limbs_to_fr(engine.ScalarInnerProduct.inner_product(l, r))
-    if exp is not None:
-        assert got == exp
-    else:   # linearity: <l, r> = <l[:k], r[:k]> + <l[k:], r[k:]>
+    assert got == exp
+    if n > 2000:   # linearity: <l, r> = <l[:k], r[:k]> + <l[k:], r[k:]>
         k = 777
         assert got == (orc.limbs_to_fr(engine.ScalarInnerProduct.inner_product(l[:k], r[:k])) + orc.limbs_to_fr(engine.ScalarInnerProduct.inner_product(l[k:], r[k:]))) % orc.R
-        assert orc.limbs_to_fr(engine.ScalarInnerProduct.inner_product(l[:k], r[:k])) == sum(orc.limbs_to_fr(a) * orc.limbs_to_fr(b) for a, b in zip(l[:k], r[:k])) % orc.R
+        assert orc.limbs_to_fr(engine.ScalarInnerProduct.inner_product(l[:k], r[:k])) == sum(a * b for a, b in zip(li[:k], ri[:k])) % orc.R
     if n:
         with pytest.raises(engine.InnerProductError):
             engine.ScalarInnerProduct.inner_product(l, r[:-1])

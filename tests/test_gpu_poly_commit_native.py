@@ -206,6 +206,34 @@ def test_kzg_65535_equals_the_python_path(engine, orc, P, N):
     srs.close()
 
 
+def test_kzg_ragged_scan_sizes(engine, orc, P, N):
+    """the quotient scan where a lane owns several chunks and the tail is ragged (msm_batch.hpp: per = ceil(chunks / 256) > 1 with a short last lane, empty lanes
+    above it and a last chunk of fewer than 64 coefficients), through the public entry points: p(z) against Python Horner, the proof against the oracle's MSM of the
+    Python-integer quotient over the handle's powers (pinned to the oracle by test_kzg)"""
+    size = 64 * 513 + 5
+    rng = random.Random(513)
+    alpha, beta = rng.randrange(1, orc.R), rng.randrange(1, orc.R)
+    srs = N.KZG.setup(P.frs([alpha])[0], P.frs([beta])[0], size - 1)
+    powers = srs.kzg_powers(); v = srs.verifier_key()
+    assert len(powers) == size
+    call = engine.synth_fr(41, size); pall = _ints(orc, call)
+    for m in (64 * 256 + 1, 64 * 257 + 63, size):
+        c, p = np.ascontiguousarray(call[:m]), pall[:m]
+        assert p[m - 1] != 0
+        com = N.KZG.commit(srs, c)
+        for z in (rng.randrange(2, orc.R - 1), orc.R - 1):
+            s, acc = [0] * m, 0                                                          # suffix Horner: the quotient is s[1:], p(z) = s[0]
+            for k in range(m - 1, -1, -1):
+                acc = (acc * z + p[k]) % orc.R; s[k] = acc
+            fz = P.frs([z])[0]
+            proof, val = N.KZG.open(srs, c, fz)
+            assert _int(orc, val) == s[0] == _horner(orc, p, z), (m, hex(z))
+            assert _same_g1(orc, proof, orc.msm_g1_a(np.ascontiguousarray(powers[:m - 1]), P.frs(s[1:]))), (m, hex(z))
+            assert N.KZG.verify(v, com, fz, val, proof), (m, hex(z))
+            assert not N.KZG.verify(v, com, fz, P.frs([(s[0] + 1) % orc.R])[0], proof), (m, hex(z))
+    srs.close()
+
+
 # ---------------------------------------------------------------------------------------------------------------- bivariate
 def _cmp_ssm(orc, got, exp):
     assert np.array_equal(got["com_gt"], exp["com_gt"]) and np.array_equal(got["tr"], exp["tr"]) and np.array_equal(got["kzg_c"], exp["kzg_c"])
