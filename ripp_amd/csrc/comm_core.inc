@@ -255,7 +255,7 @@ int32_t comm_allgather_live(Engine* e, const void* send, void* recv, size_t byte
     HIPCHK(hipMemcpyAsync(g_comm.send.p, g_comm.hsend.p, bytes, hipMemcpyHostToDevice, g_comm.st));
     NCCLCHK(g_comm.pAllGather(g_comm.send.p, g_comm.recv.p, bytes, ncclUint8, g_comm.nccl, g_comm.st));
     HIPCHK(hipMemcpyAsync(g_comm.hrecv.p, g_comm.recv.p, total, hipMemcpyDeviceToHost, g_comm.st));
-    const double t0 = now_ms(), limit = (double)(e && e->comm_timeout_ms ? e->comm_timeout_ms : 60000);
+    const double t0 = now_ms(), limit = (double)(e && e->cfg.pub.comm_timeout_ms ? e->cfg.pub.comm_timeout_ms : 60000);
     for (uint32_t spins = 0;; ++spins) {
         const hipError_t q = hipStreamQuery(g_comm.st);
         if (q == hipSuccess) break;

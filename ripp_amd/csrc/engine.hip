@@ -47,6 +47,7 @@
 #include "vm_fold2.hpp"
 #include "host_fs.hpp"
 #include "wire.hpp"
+#include "config.hpp"
 
 using namespace ripp;
 
@@ -278,42 +279,25 @@ struct Engine {
     // pinned staging buffers per call cost ~10 ms of every host-slice proof -- most of it the frees, AFTER the digest, where nothing hides them
     // (host slices 442.6 ms against 430.3 ms for the same proof on a resident job).  Freed by ripp_release_scratch / ripp_shutdown like the other scratch.
     struct JobBufCache { DevBuf d[15]; PinBuf p[4]; bool full = false; void release() { for (DevBuf& b : d) b.release(); for (PinBuf& b : p) b.release(); full = false; } } job_cache;
-    size_t msm_chunk_min = (size_t)1 << 20;                               // host-slice MSMs of >= this many G1 bases (half as many G2 bases: the same bytes) run as two halves on two streams (msm_impl: the second half's upload beside the first half's additions)
-    size_t msm_lds_sort_min = 0;                                          // MSMs of >= this many terms (after the GLV / GLS split) sort through LDS tiles (msm.hpp k_msm_hist_lds / k_msm_scatter_lds); the lane-per-term sort below it (A/B)
     const void* g2tab_hi = nullptr; size_t g2tab_half = 0;               // in-round G2 fold tables built ahead of the challenge (fold_g2_table_build): the vector half they were built over
-    size_t vm_scale_max = (size_t)1 << 14;                                // per-element G1 scalings of <= this many elements run on the VM (measured: direct product 6.1 -> 3.8 ms at 2^13, 7.1 -> 6.2 ms at 2^14, level at 2^15)
-    size_t vm_joint_max = (size_t)1 << 13;                                // folds with <= this many outputs (and more than vm_fold_max) use the joint one-group-per-element VM forms
-    size_t lp_fq_min = 0;                 // pairs per launch from which k_line_products_q replaces k_line_products: always (11 % faster per launch: 5.8 vs 6.5 ms at the proof's launch
-                                          // mix; it keeps ~47 dwords per lane in scratch, which costs HBM traffic, not time -- the kernel is issue-bound).  RIPP_LP_FQ_MIN=4294967295 / RIPP_NO_FQ select k_line_products
-    size_t ml_fq_min = 0;                 // pairs per launch from which k_miller_lines_q (fq_miller.hpp) replaces k_miller_lines: every throughput launch (the VM kernel covers the small ones)
-    size_t fq_min_g1 = (size_t)1 << 12;   // ... the G1 NAF fold (one 128-step chain per lane either way): the carry-free kernel wherever the lane-per-element form runs at all
-    size_t fq_min = (size_t)1 << 15;      // the carry-free fold kernels (fq_curve.hpp, fq_curve2.hpp): from 2^15 outputs (round 4 of an n = 2^20 proof: 5.4 -> 3.9 ms; below that the 12 x 32-bit forms have the shorter chains)
-    size_t fold_tab_min = 32768;          // G2 folds of at least this many elements build in-round odd-multiple tables
-    size_t msm_vm_merge_max = 16384;      // buckets (all windows) up to which the bucket merge runs on the field VM
     hipStream_t stream5 = nullptr;        // second G2 fold of a small GIPA round (own scratch there, so it need not queue behind the first)
     hipEvent_t ev_join5 = nullptr;
     Fp12* pinned_rows = nullptr;          // pinned host landing zone for per-step products
     size_t pinned_rows_cap = 0;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_lines, ev_prod;   // per-launch event pairs of the two dominant kernels
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_fold_async;       // folds nobody waited for (pipelined / pre-evaluated rounds): their device time is added to stats.fold_ms when the proof ends
-    size_t tail_pipe_max = (size_t)1 << 11;                               // SIPP rounds of at most this length run pipelined (job_tail_enqueue); 0 = off
-    size_t vm_tree_max = (size_t)1 << 16;                                 // tree levels with <= this many products use the VM Fp12 multiplier
-    size_t vm_fold_max = (size_t)1 << 11;                                 // folds with <= this many outputs use the VM scalar multiplications
     DevBuf vm_flag;
-    size_t vm_lines_max = (size_t)1 << 15;                                // launches with <= this many pairs use the 16-lanes-per-pair VM line kernel (measured crossover)
-    size_t gls_split_max = (size_t)1 << 14;                               // rounds with <= this many outputs use the 4-lane GLS fold
     size_t max_pairs_per_batch = (size_t)1 << 19;                        // lines buffer cap: 2^19 pairs * 19.6 KB = 10.3 GB (pairs_cap() lowers it when the device is short of memory)
     // ---- memory-aware degradation (ripp_config.mem_cap_bytes) --------------------------------------------------------------
     // The optional structures of a large proof are sized against what the device can still give: the line buffer first (without it nothing runs:
     // pairs_cap halves the batch until it fits), then the round-0 fold tables (13.6 KB per element in the three-quarter form: job_precompute_round0
     // steps down to half-vector tables of four multiples, then to the two pre-doubled bases, then to nothing), the in-round G2 tables
-    // (fold_g2_table_pays).  Every tier computes the same group elements.  mem_cap = 0: what hipMemGetInfo reports free, less a margin.
-    size_t mem_cap = 0;
+    // (fold_g2_table_pays).  Every tier computes the same group elements.  mem_cap_bytes = 0: what hipMemGetInfo reports free, less a margin.
     int mem_tier = 0;                     // the deepest fall-back this call took: 0 none, 1 half-vector tables, 2 pre-doubled bases only, 3 no round-0 precomputation; +8: the line buffer was cut; +16: an in-round G2 table fold took the split form
     bool mem_fits(size_t need, size_t held) const {
         if (need <= held) return true;
         const size_t extra = need - held;
-        if (mem_cap) return g_dev_bytes.load(std::memory_order_relaxed) + extra <= mem_cap;
+        if (cfg.pub.mem_cap_bytes) return g_dev_bytes.load(std::memory_order_relaxed) + extra <= cfg.pub.mem_cap_bytes;
         size_t fr = 0, tot = 0;
         if (hipMemGetInfo(&fr, &tot) != hipSuccess) return true;
         return extra + std::max<size_t>((size_t)2 << 30, tot / 50) <= fr;
@@ -334,99 +318,18 @@ struct Engine {
     // TIPAWithSSM sub-proofs) run side by side, each driven by its own host thread, instead of taking turns waiting for host and device.
     // In-process multi-device dispatch of the stateless trait calls (ripp_config.n_devices): one more Engine per extra device, each driven by its own host
     // thread for the duration of one call (device_slots / run_on_devices below).  RIPP_VIRTUAL_DEVICES=G (one-GPU test rig): G slots, all on the bound device.
-    std::vector<Engine*> peers; bool virtual_devices = false;
+    std::vector<Engine*> peers;
     Engine* aux = nullptr;
     Engine* aux_engine() {
         if (!aux) { Engine* a = new Engine(); if (a->init(device) != RIPP_OK) { delete a; return nullptr; } aux = a; }
         aux->refresh_switches(); aux->stats = ripp_stats{};
         return aux;
     }
-    // run-time switches: read from the environment ONCE per C-ABI call (get_engine), never inside round loops
-    struct Switches { bool no_vm = false, no_precompute = false, no_fold_tables = false, no_msm_glv = false, lp_one_lane = false, no_endo = false, no_fq = false, no_xscale = false, no_share = false, no_fuse = false, no_prebuild = false, fuse_tables = false, no_job_cache = false, no_lp_kara = false, no_msm_batch = false; } sw;
-    // crossover sizes: the member initialisers above are the defaults, the environment overrides them PER CALL (a test or
-    // an A/B run flips them on a live engine)
-    struct Sizes { size_t vm_lines_max, vm_fold_max, vm_tree_max, gls_split_max, msm_vm_merge_max, fold_tab_min, fq_min, lp_fq_min, vm_joint_max, vm_scale_max, tail_pipe_max, ml_fq_min, fq_min_g1, msm_lds_sort_min, msm_chunk_min; } defaults{};
-    MsmTune msm_tune;
-    // First-tier rounds of the transparent polynomial commitment (tpc_api.inc): key vectors of at least this length commit with the crossed two-row
-    // batch pass, shorter ones with two single MSMs on two streams.  tools/tpc_first_tier_ab.py tabulates both forms per round length in
-    // profiles/tpc_first_tier_ab.txt (crossed ahead at key length 4096, behind at 2048, level below); the bound has not been moved on that one table yet, so no
-    // round takes the crossed form by default.  RIPP_TPC_CROSS_MIN overrides the bound per call (2: every round crossed).
-    static constexpr size_t TPC_CROSS_MIN = ~(size_t)0;
-    size_t tpc_cross_min = TPC_CROSS_MIN;
-    // Rounds of the GIPA prover with a committed scalar vector (gipa_mexp_api.inc): vectors of at least this length run the round's four G1 MSMs as ONE
-    // four-row pass of the batched pipeline (gipa_mexp.hpp), shorter ones as four single MSMs on two side streams.  profiles/gipa_mexp_ab.txt
-    // (tools/gipa_mexp_ab.py): with every round in one pass the whole proof's median is below the four-MSM form's minimum at every measured n = 2^4 .. 2^16
-    // (0.85 - 0.93 of it); 16 is the shortest measured length.  RIPP_GIPA_MEXP_BATCH_MIN overrides the bound per call (2: every round in one pass).
-    static constexpr size_t GIPA_MEXP_BATCH_MIN = 16;
-    size_t gipa_mexp_batch_min = GIPA_MEXP_BATCH_MIN;
-    // Rounds of the TIPA prover for scalar products (tipa_scalar_api.inc): key vectors of at least this length commit with ONE crossed two-row pass of the batched
-    // pipeline in G2 (tipa_scalar.hpp) followed by one in G1, shorter ones (and every round under the legacy MSM switches) with two single MSMs per group on two
-    // side streams.  tools/tipa_scalar_ab.py tabulates both forms in profiles/tipa_scalar_ab.txt (whole proofs, n = 2^4 .. 2^16): the crossed form is within a few
-    // per cent of the two-MSM form either way and NOT ahead at the longest measured size, so by the rule in that file's header no round takes it by default.
-    // RIPP_TIPA_SCALAR_CROSS_MIN overrides the bound per call (2: every round crossed).
-    static constexpr size_t TIPA_SCALAR_CROSS_MIN = ~(size_t)0;
-    size_t tipa_scalar_cross_min = TIPA_SCALAR_CROSS_MIN;
-    // the hash-window look-ahead plan and a few whole-call choices (ripp_config: look_eighths, ranks_per_device, look_static, quiet_waits, agg_sequential, scale_no_fq)
+    // run-time configuration (config.hpp): resolved ONCE per C-ABI call (get_engine), never inside round loops
+    Config cfg = config_defaults();
+    void refresh_switches() { cfg = config_resolve(g_cfg_set ? &g_cfg : nullptr); }
+    MsmTune msm_tune() const { return {cfg.pub.msm_c, cfg.pub.msm_ch, cfg.pub.msm_gmin}; }
     double cal_ms_per_pair = 0, cal_hash_bytes_per_ms = 0;        // look_plan's rates as measured by the last large proof of this process (0: not yet)
-    int look_eighths = -1; double ranks_per_device = 1.0; bool look_static = false, quiet_waits_cfg = false, agg_sequential = false, scale_no_fq = false;
-    int hot_workers_cfg = 0;               // 0 automatic, 1 always, 2 never (ripp_config.hot_workers / RIPP_HOT_WORKERS)
-    uint32_t comm_timeout_ms = 0, plan_derate_pct = 0, n_devices_cfg = 0;      // ripp_config members of the same names (RIPP_COMM_TIMEOUT_MS, RIPP_PLAN_DERATE_PCT, RIPP_N_DEVICES)
-    // Precedence: built-in defaults < ripp_configure() < environment variables (a debug / A-B override).  This function is the ONLY place of the
-    // library that reads RIPP_* configuration from the environment (RIPP_TRACE aside), once per C-ABI call (get_engine) -- never inside a proof.
-    void refresh_switches() {
-        msm_tune = MsmTune();
-        vm_lines_max = defaults.vm_lines_max; vm_fold_max = defaults.vm_fold_max; vm_tree_max = defaults.vm_tree_max; gls_split_max = defaults.gls_split_max;
-        msm_vm_merge_max = defaults.msm_vm_merge_max; fold_tab_min = defaults.fold_tab_min; fq_min = defaults.fq_min; lp_fq_min = defaults.lp_fq_min; vm_joint_max = defaults.vm_joint_max;
-        vm_scale_max = defaults.vm_scale_max; tail_pipe_max = defaults.tail_pipe_max; ml_fq_min = defaults.ml_fq_min; fq_min_g1 = defaults.fq_min_g1; msm_lds_sort_min = defaults.msm_lds_sort_min; msm_chunk_min = defaults.msm_chunk_min;
-        sw = Switches(); look_eighths = -1; ranks_per_device = 1.0; look_static = quiet_waits_cfg = agg_sequential = scale_no_fq = false; mem_cap = 0; hot_workers_cfg = 0; comm_timeout_ms = plan_derate_pct = n_devices_cfg = 0;
-        if (g_cfg_set) {
-            const ripp_config& c = g_cfg;
-            sw.no_vm = c.no_vm; sw.no_precompute = c.no_precompute; sw.no_fold_tables = c.no_fold_tables; sw.no_msm_glv = c.no_msm_glv; sw.lp_one_lane = c.lp_one_lane;
-            sw.no_endo = c.no_endo; sw.no_fq = c.no_fq; sw.no_xscale = c.no_xscale; sw.no_share = c.no_share; sw.no_fuse = c.no_fuse; sw.fuse_tables = c.fuse_tables; scale_no_fq = c.scale_no_fq; agg_sequential = c.agg_sequential; look_static = c.look_static; quiet_waits_cfg = c.quiet_waits;
-            look_eighths = c.look_eighths; ranks_per_device = c.ranks_per_device > 1 ? (double)c.ranks_per_device : 1.0;
-            msm_tune.c = c.msm_c; msm_tune.ch = c.msm_ch; msm_tune.gmin = c.msm_gmin; sw.no_prebuild = c.no_prebuild;
-            mem_cap = (size_t)c.mem_cap_bytes; hot_workers_cfg = (int)c.hot_workers; sw.no_job_cache = c.no_job_cache != 0;
-            sw.no_lp_kara = c.no_lp_karatsuba != 0; comm_timeout_ms = c.comm_timeout_ms; plan_derate_pct = c.plan_derate_pct; n_devices_cfg = c.n_devices;
-            vm_lines_max = c.vm_lines_max; vm_fold_max = c.vm_fold_max; vm_tree_max = c.vm_tree_max; gls_split_max = c.gls_split_max; msm_vm_merge_max = c.msm_vm_merge_max; fold_tab_min = c.fold_tab_min;
-            fq_min = c.fq_min; lp_fq_min = c.lp_fq_min; vm_joint_max = c.vm_joint_max; vm_scale_max = c.vm_scale_max; tail_pipe_max = c.tail_pipe_max; ml_fq_min = c.ml_fq_min; fq_min_g1 = c.fq_min_g1; msm_lds_sort_min = c.msm_lds_sort_min; msm_chunk_min = c.msm_chunk_min;
-        }
-        { const char* s; if ((s = std::getenv("RIPP_MSM_C"))) msm_tune.c = std::atoi(s); if ((s = std::getenv("RIPP_MSM_CH"))) msm_tune.ch = (uint32_t)std::strtoul(s, nullptr, 10); if ((s = std::getenv("RIPP_MSM_GMIN"))) msm_tune.gmin = (uint32_t)std::strtoul(s, nullptr, 10); }
-        auto env_sz = [](const char* k, size_t& v) { if (const char* s = std::getenv(k)) v = (size_t)std::strtoull(s, nullptr, 10); };
-        env_sz("RIPP_VM_LINES_MAX", vm_lines_max); env_sz("RIPP_VM_FOLD_MAX", vm_fold_max); env_sz("RIPP_VM_TREE_MAX", vm_tree_max);
-        env_sz("RIPP_GLS_SPLIT_MAX", gls_split_max); env_sz("RIPP_MSM_VM_MERGE_MAX", msm_vm_merge_max); env_sz("RIPP_FOLD_TAB_MIN", fold_tab_min);
-        env_sz("RIPP_FQ_MIN", fq_min); env_sz("RIPP_LP_FQ_MIN", lp_fq_min); env_sz("RIPP_VM_JOINT_MAX", vm_joint_max);
-        env_sz("RIPP_MSM_LDS_SORT_MIN", msm_lds_sort_min); env_sz("RIPP_MSM_CHUNK_MIN", msm_chunk_min);
-        env_sz("RIPP_VM_SCALE_MAX", vm_scale_max); env_sz("RIPP_TAIL_PIPE_MAX", tail_pipe_max); env_sz("RIPP_ML_FQ_MIN", ml_fq_min); env_sz("RIPP_FQ_MIN_G1", fq_min_g1);
-        auto env_on = [](const char* k, bool& v) { if (std::getenv(k)) v = true; };
-        env_on("RIPP_NO_VM", sw.no_vm); env_on("RIPP_NO_PRECOMPUTE", sw.no_precompute); env_on("RIPP_NO_FOLD_TABLES", sw.no_fold_tables); env_on("RIPP_NO_MSM_GLV", sw.no_msm_glv);
-        env_on("RIPP_LP_ONE_LANE", sw.lp_one_lane);
-        env_on("RIPP_NO_ENDO", sw.no_endo);            // plain scalar multiplications in the folds / scaling (no GLV, no psi)
-        env_on("RIPP_NO_XSCALE", sw.no_xscale);        // G2 folds always on the plain vector with the full-width x^-1
-        env_on("RIPP_NO_LP_KARA", sw.no_lp_kara);      // stage 2 of the pairing product with the six-product sums of k_line_products_q instead of the Karatsuba form (BLS12-381)
-        env_on("RIPP_NO_FQ", sw.no_fq);                // the 12 x 32-bit forms of the kernels that have a carry-free twin (fq_curve.hpp)
-        env_on("RIPP_FUSE_TABLES", sw.fuse_tables);    // build the three-quarter tables whatever the look-ahead plan (tests: round 0 then folds ALONE over them when x1 is late)
-        env_on("RIPP_NO_JOB_CACHE", sw.no_job_cache);  // one-shot proofs allocate and free their job buffers per call (ripp_config.no_job_cache)
-        env_sz("RIPP_MEM_CAP_BYTES", mem_cap);         // device memory the library may hold (ripp_config.mem_cap_bytes; 0 = automatic)
-        if (const char* s = std::getenv("RIPP_HOT_WORKERS")) hot_workers_cfg = std::atoi(s) ? 1 : 2;
-        { auto env_u32 = [](const char* k, uint32_t& v) { if (const char* s = std::getenv(k)) v = (uint32_t)std::strtoul(s, nullptr, 10); };
-          env_u32("RIPP_COMM_TIMEOUT_MS", comm_timeout_ms); env_u32("RIPP_PLAN_DERATE_PCT", plan_derate_pct); env_u32("RIPP_N_DEVICES", n_devices_cfg);
-          virtual_devices = false; if (const char* s = std::getenv("RIPP_VIRTUAL_DEVICES")) { n_devices_cfg = (uint32_t)std::strtoul(s, nullptr, 10); virtual_devices = true; } }
-        tpc_cross_min = TPC_CROSS_MIN; env_sz("RIPP_TPC_CROSS_MIN", tpc_cross_min);      // crossed two-row commitments of the first-tier rounds from this key length on (A/B)
-        tipa_scalar_cross_min = TIPA_SCALAR_CROSS_MIN; env_sz("RIPP_TIPA_SCALAR_CROSS_MIN", tipa_scalar_cross_min);      // crossed G2 / G1 commitments of a scalar-product TIPA round from this key length on (A/B)
-        gipa_mexp_batch_min = GIPA_MEXP_BATCH_MIN; env_sz("RIPP_GIPA_MEXP_BATCH_MIN", gipa_mexp_batch_min);      // four-row pass of a committed-scalar GIPA round from this vector length on (A/B)
-        env_on("RIPP_NO_MSM_BATCH", sw.no_msm_batch);  // batched shared-base MSMs as a loop of single MSMs over the rows (A/B; the form the legacy MSM switches select too)
-        env_on("RIPP_NO_PREBUILD", sw.no_prebuild);    // in-round G2 fold tables after the challenge (fold_g2_table), not in the host phase before it (job_prebuild_g2_tables)
-        env_on("RIPP_NO_FUSE", sw.no_fuse);            // rounds 0 and 1 always fold one after the other (no three-quarter tables, no job_fold_fused)
-        env_on("RIPP_NO_SHARE", sw.no_share);          // every pairing product walks its own G2 chain (no ChainSets grouping, no merged round 0 + look-ahead)
-        env_on("RIPP_SCALE_NO_FQ", scale_no_fq); env_on("RIPP_AGG_SEQUENTIAL", agg_sequential); env_on("RIPP_LOOK_STATIC", look_static); env_on("RIPP_QUIET_WAITS", quiet_waits_cfg);
-        if (const char* s = std::getenv("RIPP_LOOK_ITEMS")) look_eighths = 8 * std::max(0, std::atoi(s));            // whole (round, side) items
-        if (const char* s = std::getenv("RIPP_LOOK_EIGHTHS")) look_eighths = std::max(0, std::atoi(s));               // 8 k + f: k items and f/8 of the next
-        if (const char* s = std::getenv("RIPP_RANKS_PER_DEVICE")) ranks_per_device = std::max(1.0, std::atof(s));
-        // (both builds run the carry-free throughput kernels: fq_curve2.hpp FQ2_BETA, fq_miller.hpp / fq_line_products.hpp per twist type)
-#if !defined(RIPP_AB_KERNELS) || defined(RIPP_BLS12_377)
-        sw.lp_one_lane = false;                        // k_line_products1 is compiled into A/B builds of the BLS12-381 library only (-DRIPP_AB_KERNELS)
-#endif
-    }
 
     int32_t init(int dev) {
         int n = 0;
@@ -441,7 +344,6 @@ struct Engine {
         HIPCHK(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&ev_join, hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&ev_join3, hipEventDisableTiming));
         HIPCHK(hipEventCreate(&ev_t0)); HIPCHK(hipEventCreate(&ev_t1));
         { hipDeviceProp_t pr; if (hipGetDeviceProperties(&pr, dev) == hipSuccess) n_simd = pr.multiProcessorCount * 4; }
-        defaults = Sizes{vm_lines_max, vm_fold_max, vm_tree_max, gls_split_max, msm_vm_merge_max, fold_tab_min, fq_min, lp_fq_min, vm_joint_max, vm_scale_max, tail_pipe_max, ml_fq_min, fq_min_g1, msm_lds_sort_min, msm_chunk_min};
         refresh_switches();
         device = dev;
         return RIPP_OK;
@@ -503,18 +405,18 @@ struct Engine {
     int32_t scale_g1_dev(const G1A* base, uint32_t base_stride, const Fr* k, size_t n, G1J* out, hipStream_t st = nullptr) {
         if (n == 0) return RIPP_OK;
         if (!st) st = stream;
-        if (sw.no_endo) {                                     // 255-bit double-and-add (the reference's `a.mul(r)`, sipp/src/lib.rs:61-65)
+        if (cfg.pub.no_endo) {                                     // 255-bit double-and-add (the reference's `a.mul(r)`, sipp/src/lib.rs:61-65)
             hipLaunchKernelGGL(HIP_KERNEL_NAME(k_scale_pts<Fp>), dim3(nblk(n, 256)), dim3(256), 0, st, base, base_stride, k, (uint32_t)n, out);
             HIPCHK(hipGetLastError());
             return RIPP_OK;
         }
-        if (n <= vm_scale_max && !sw.no_vm) {                  // few elements: one VM group per element instead of a lone lane (~1.3 ms instead of ~3.9 ms)
+        if (n <= cfg.pub.vm_scale_max && !cfg.pub.no_vm) {                  // few elements: one VM group per element instead of a lone lane (~1.3 ms instead of ~3.9 ms)
             hipLaunchKernelGGL(k_vm_scale_g1, dim3(nblk(n, 4 * VM_EPW)), dim3(256), 4 * VM_EPW * VM_SCALE_SLOTS * sizeof(VmSlot), st, base, base_stride, k, (uint32_t)n, out);
             HIPCHK(hipGetLastError());
             return RIPP_OK;
         }
         int32_t rc = scale_tab.reserve((size_t)SCALE_TAB * G1J_CHUNKS * n * sizeof(uint4)); if (rc) return rc;
-        if (!sw.no_fq && !scale_no_fq)      // the carry-free twin (fq_scale.hpp)
+        if (!cfg.pub.no_fq && !cfg.pub.scale_no_fq)      // the carry-free twin (fq_scale.hpp)
         {
             if ((rc = scale_flags.reserve(n + 16))) return rc;
             hipLaunchKernelGGL(k_scale_g1_glv_q, dim3(nblk(n, 256)), dim3(256), 0, st, base, base_stride, k, (uint32_t)n, scale_tab.as<uint4>(), out, scale_flags.as<uint8_t>());
@@ -547,9 +449,9 @@ struct Engine {
     template <class F> int32_t msm_launch(MsmScratch& ms, hipStream_t st, const Affine<F>* bases, const Fr* scalars, size_t n, const std::function<int32_t()>* bases_arrive = nullptr) {
         if (!ms.host_out) HIPCHK(hipHostMalloc(&ms.host_out, sizeof(G2J), hipHostMallocDefault));
         if (n == 0) { *reinterpret_cast<Jac<F>*>(ms.host_out) = jac_inf<F>(); return bases_arrive ? (*bases_arrive)() : RIPP_OK; }
-        const bool no_glv = sw.no_msm_glv;
+        const bool no_glv = cfg.pub.no_msm_glv;
         const size_t nreal = n;
-        const MsmPlan p = msm_plan(nreal, no_glv ? 1 : std::is_same<F, Fp>::value ? 2 : 4, msm_tune);
+        const MsmPlan p = msm_plan(nreal, no_glv ? 1 : std::is_same<F, Fp>::value ? 2 : 4, msm_tune());
         n = p.n;                                                                  // terms (2 * nreal in the GLV form, 4 * nreal in the GLS form)
         const size_t nwb = (size_t)p.nwin * p.nb;
         const uint32_t max_slots = (uint32_t)(n / p.ch + std::min<size_t>(p.nb, n) + 1);
@@ -562,7 +464,7 @@ struct Engine {
             (rc = ms.seg2.reserve((size_t)p.nwin * ((nseg + MSM_SEG_FAN - 1) / MSM_SEG_FAN) * sizeof(Jac<F>))) ||
             (rc = ms.win.reserve(64 * sizeof(Jac<F>))) || (rc = ms.out.reserve(sizeof(Jac<F>)))) return rc;
         HIPCHK(hipMemsetAsync(ms.hist.p, 0, nwb * 4, st));
-        const bool lds_sort = n >= msm_lds_sort_min && p.nb <= 8192;   // count and rank through LDS tiles (msm.hpp; measured no slower at any size, 2.3 ms faster at n = 2^20)
+        const bool lds_sort = n >= cfg.pub.msm_lds_sort_min && p.nb <= 8192;   // count and rank through LDS tiles (msm.hpp; measured no slower at any size, 2.3 ms faster at n = 2^20)
         const uint32_t tile = msm_sort_tile(p);
         hipLaunchKernelGGL(k_msm_digits, dim3(nblk(nreal, 256)), dim3(256), 0, st, scalars, p, ms.digits.as<uint16_t>(), lds_sort ? nullptr : ms.hist.as<uint32_t>());
         if (lds_sort) hipLaunchKernelGGL(k_msm_hist_lds, dim3(nblk(n, tile), p.nwin), dim3(MSM_SORT_BLOCK), 0, st, ms.digits.as<uint16_t>(), p, tile, ms.hist.as<uint32_t>());
@@ -572,9 +474,9 @@ struct Engine {
         if (bases_arrive && (rc = (*bases_arrive)())) return rc;
         // RIPP_NO_VM keeps every stage on single lanes in Jacobian coordinates (the A/B and fallback form); otherwise the stages after
         // the gather work on homogeneous coordinates and the ones with few points run on the field VM (msm.hpp)
-        const bool hom = !sw.no_vm;
+        const bool hom = !cfg.pub.no_vm;
         const size_t vm_lds = 4 * VM_EPW * VmCurve<F>::SLOTS * sizeof(VmSlot);
-        if (!sw.no_fq) {        // gathered additions on the carry-free form over the extended base array (fq_msm.hpp), both curves
+        if (!cfg.pub.no_fq) {        // gathered additions on the carry-free form over the extended base array (fq_msm.hpp), both curves
             const int split = (int)(n / nreal);
             if ((rc = ms.ext.reserve(n * sizeof(Affine<F>))) || (rc = ms.flags.reserve((size_t)p.nwin * max_slots + 16))) return rc;
             hipLaunchKernelGGL(HIP_KERNEL_NAME(k_msm_extend_q<F>), dim3(nblk(nreal, 256), split), dim3(256), 0, st, bases, (uint32_t)nreal, split, ms.ext.as<QAff<F>>());
@@ -599,7 +501,7 @@ struct Engine {
         for (uint32_t stride = 1; passes < (uint32_t)MSM_GROUP_PASSES && n / p.ch + 1 > (size_t)p.gmin * stride; stride *= MSM_SLOT_GROUP, ++passes)
             hipLaunchKernelGGL(HIP_KERNEL_NAME(k_msm_slot_group<F>), dim3(nblk(max_slots, 64), p.nwin), dim3(64), 0, st, p, ms.hist.as<uint32_t>(),
                                ms.slotoffs.as<uint32_t>(), ms.spw.as<uint32_t>(), ms.slots.as<Jac<F>>(), max_slots, stride, hom);
-        if (hom && nwb <= msm_vm_merge_max)                                        // few buckets: 16 lanes per bucket still fit the chip
+        if (hom && nwb <= cfg.pub.msm_vm_merge_max)                                        // few buckets: 16 lanes per bucket still fit the chip
             hipLaunchKernelGGL(HIP_KERNEL_NAME(k_msm_vm_merge<F>), dim3(nblk(p.nb, 4 * VM_EPW), p.nwin), dim3(256), vm_lds, st, p, ms.hist.as<uint32_t>(), ms.slotoffs.as<uint32_t>(),
                                ms.slots.as<Jac<F>>(), max_slots, ms.buckets.as<Jac<F>>(), passes);
         else
@@ -651,10 +553,10 @@ struct Engine {
     // row 1 = (0, m[:h]).  The legacy switches have no crossed form: the caller asks msm_batch_legacy() first and runs two msm_launch calls instead.
     // quad_len != 0: the four-row form of gipa_mexp.hpp -- rows = 4, cols = 2 quad_len bases (ck_b | m_a), scalars = ONE vector m_b of quad_len elements.  Like the
     // crossed form it needs the batched pipeline and one chunk: the caller asks msm_batch_legacy() and msm_quad_fits() / msm_rows_fit() first.
-    bool msm_batch_legacy() const { return sw.no_msm_batch || sw.no_msm_glv || sw.no_fq || sw.no_vm; }
+    bool msm_batch_legacy() const { return cfg.no_msm_batch || cfg.pub.no_msm_glv || cfg.pub.no_fq || cfg.pub.no_vm; }
     // `rows` rows over `cols` bases run as ONE chunk: grid.y, the 32-bit slot index of the fix-up kernels and the memory budget
     template <class F> bool msm_rows_fit(size_t cols, size_t rows) {
-        const MsmPlan p = msm_plan_batch(cols, msm_batch_split<F>(), rows, msm_tune);
+        const MsmPlan p = msm_plan_batch(cols, msm_batch_split<F>(), rows, msm_tune());
         const size_t max_slots = (size_t)p.n / p.ch + std::min<size_t>(p.nb, p.n) + 1;
         if (rows * (size_t)p.nwin > 65535 || rows * (size_t)p.nwin * max_slots >= ((size_t)1 << 32)) return false;
         MsmScratch& ms = msm_batch;
@@ -680,7 +582,7 @@ struct Engine {
             return RIPP_OK;
         }
         MsmScratch& ms = msm_batch;
-        const MsmPlan p = msm_plan_batch(cols, split, rows, msm_tune);
+        const MsmPlan p = msm_plan_batch(cols, split, rows, msm_tune());
         const size_t n = p.n, max_slots = n / p.ch + std::min<size_t>(p.nb, n) + 1;
         // rows per chunk: grid.y and the 32-bit slot index of the fix-up kernels bound it first, then the memory budget (halving; one row always runs)
         size_t R = std::min<size_t>(rows, std::min<size_t>(65535 / (size_t)p.nwin, (((size_t)1 << 32) - 1) / ((size_t)p.nwin * max_slots)));
@@ -727,7 +629,7 @@ struct Engine {
             for (uint32_t gs = 1; passes < (uint32_t)MSM_GROUP_PASSES && n / p.ch + 1 > (size_t)p.gmin * gs; gs *= MSM_SLOT_GROUP, ++passes)
                 hipLaunchKernelGGL(HIP_KERNEL_NAME(k_msm_slot_group<F>), dim3(nblk(max_slots, 64), pb.nwin), dim3(64), 0, st, pb, ms.hist.as<uint32_t>(),
                                    ms.slotoffs.as<uint32_t>(), ms.spw.as<uint32_t>(), ms.slots.as<Jac<F>>(), (uint32_t)max_slots, gs, true);
-            if (nwb <= msm_vm_merge_max)
+            if (nwb <= cfg.pub.msm_vm_merge_max)
                 hipLaunchKernelGGL(HIP_KERNEL_NAME(k_msm_vm_merge<F>), dim3(nblk(p.nb, 4 * VM_EPW), pb.nwin), dim3(256), vm_lds, st, pb, ms.hist.as<uint32_t>(), ms.slotoffs.as<uint32_t>(),
                                    ms.slots.as<Jac<F>>(), (uint32_t)max_slots, ms.buckets.as<Jac<F>>(), passes);
             else
@@ -759,14 +661,14 @@ struct Engine {
         {
             PairSets ps{}; for (int p = 0; p < nprod; ++p) { ps.a[p] = a[p] + off; ps.b[p] = b[p] + off; }
             if ((rc = mark(ev_lines, true)) != RIPP_OK) return rc;
-            if (m * nprod <= vm_lines_max && !sw.no_vm)
+            if (m * nprod <= cfg.pub.vm_lines_max && !cfg.pub.no_vm)
                 hipLaunchKernelGGL(k_vm_miller_lines, dim3(nblk(m, 4 * VM_EPW), nprod), dim3(256), 4 * VM_EPW * VM_LINES_SLOTS * sizeof(VmSlot), stream, ps, (uint32_t)m, lines.as<uint4>(), stride);
-            else if (!sw.no_fq && m * nprod >= ml_fq_min) {       // the carry-free twin (fq_miller.hpp): ~25 % fewer instructions on an issue-bound kernel
+            else if (!cfg.pub.no_fq && m * nprod >= cfg.pub.ml_fq_min) {       // the carry-free twin (fq_miller.hpp): ~25 % fewer instructions on an issue-bound kernel
                 // consecutive products over the SAME Q vector share one chain (up to MAX_SHARE P's per lane): the callers order their product lists accordingly
                 ChainSets cs{}; int ng = 0;
                 for (int p = 0; p < nprod; ++p) {
                     cs.a[p] = ps.a[p];
-                    if (!sw.no_share && ng > 0 && ps.b[p] == cs.b[ng - 1] && cs.np[ng - 1] < MAX_SHARE) ++cs.np[ng - 1];
+                    if (!cfg.pub.no_share && ng > 0 && ps.b[p] == cs.b[ng - 1] && cs.np[ng - 1] < MAX_SHARE) ++cs.np[ng - 1];
                     else { cs.b[ng] = ps.b[p]; cs.first[ng] = (uint8_t)p; cs.np[ng] = 1; ++ng; }
                 }
                 hipLaunchKernelGGL(k_miller_lines_q, dim3(nblk(m, 256), ng), dim3(256), 0, stream, cs, (uint32_t)m, lines.as<uint4>(), stride);
@@ -792,7 +694,7 @@ struct Engine {
             while (left > 0 && k < 8) { int f = 0; while (fill[f] > left) ++f; pieces[k++] = fill[f]; left -= fill[f]; }
             if (left > 0) pieces[7] += left;
         }
-        else if (m * (size_t)nprod >= ((size_t)1 << 17) && !sw.lp_one_lane) {
+        else if (m * (size_t)nprod >= ((size_t)1 << 17) && !cfg.pub.lp_one_lane) {
             if (nprod == 8) { pieces[0] = 6; pieces[1] = 2; } else if (nprod == 7) { pieces[0] = 5; pieces[1] = 2; } else if (nprod == 4) { pieces[0] = 2; pieces[1] = 2; }
         }
         int p_lo = 0;
@@ -811,18 +713,18 @@ struct Engine {
         // RIPP_LP_ONE_LANE=1 selects the one-lane-per-accumulator kernel (A/B builds only).
         // BLS12-381, throughput-sized launches: the Karatsuba form (fq_line_products_k.hpp: six lanes per accumulator, 10 accumulators per wave)
 #if !defined(RIPP_BLS12_377)
-        const bool lp_kara = !sw.no_fq && !sw.no_lp_kara && !sw.lp_one_lane && m * (size_t)np2 >= lp_fq_min;
+        const bool lp_kara = !cfg.pub.no_fq && !cfg.pub.no_lp_karatsuba && !cfg.pub.lp_one_lane && m * (size_t)np2 >= cfg.pub.lp_fq_min;
 #else
         const bool lp_kara = false;
 #endif
-        const uint32_t per_wave = sw.lp_one_lane ? 64 : lp_kara ? LK_GROUPS_PER_WAVE : LP_GROUPS_PER_WAVE;
+        const uint32_t per_wave = cfg.pub.lp_one_lane ? 64 : lp_kara ? LK_GROUPS_PER_WAVE : LP_GROUPS_PER_WAVE;
         uint32_t T = (uint32_t)std::max<size_t>(per_wave, ((size_t)n_simd * RIPP_OCC_PROD / nrows) * per_wave);
         if (T > m) T = (uint32_t)m;
         if ((rc = partA.reserve(nrows * FP12_CHUNKS * (size_t)T * sizeof(uint4))) != RIPP_OK) return rc;
         if ((rc = partB.reserve(nrows * FP12_CHUNKS * (size_t)((T + 1) / 2) * sizeof(uint4))) != RIPP_OK) return rc;
         if ((rc = mark(ev_prod, true)) != RIPP_OK) return rc;
 #if defined(RIPP_AB_KERNELS) && !defined(RIPP_BLS12_377)
-        if (sw.lp_one_lane)           // build round 1's one-lane-per-accumulator form: A/B builds only (-DRIPP_AB_KERNELS; it spills 1 248 B per lane)
+        if (cfg.pub.lp_one_lane)           // build round 1's one-lane-per-accumulator form: A/B builds only (-DRIPP_AB_KERNELS; it spills 1 248 B per lane)
             hipLaunchKernelGGL(k_line_products1, dim3(nblk(T, 64), (unsigned)nrows), dim3(64), 0, stream, lrows, stride, (uint32_t)m, partA.as<uint4>(), T);
         else
 #endif
@@ -831,7 +733,7 @@ struct Engine {
             hipLaunchKernelGGL(k_line_products_k, dim3(nblk(T, LK_GROUPS_PER_WAVE), (unsigned)nrows), dim3(64), 0, stream, lrows, stride, (uint32_t)m, partA.as<uint4>(), T);
         else
 #endif
-        if (!sw.no_fq && m * (size_t)np2 >= lp_fq_min)          // throughput-sized launches: the carry-free twin (fq_line_products.hpp), both curves
+        if (!cfg.pub.no_fq && m * (size_t)np2 >= cfg.pub.lp_fq_min)          // throughput-sized launches: the carry-free twin (fq_line_products.hpp), both curves
             hipLaunchKernelGGL(k_line_products_q, dim3(nblk(T, LP_GROUPS_PER_WAVE), (unsigned)nrows), dim3(64), 0, stream, lrows, stride, (uint32_t)m, partA.as<uint4>(), T);
         else
             hipLaunchKernelGGL(k_line_products, dim3(nblk(T, LP_GROUPS_PER_WAVE), (unsigned)nrows), dim3(64), 0, stream, lrows, stride, (uint32_t)m, partA.as<uint4>(), T);
@@ -844,7 +746,7 @@ struct Engine {
             // radix 4 while the level still fills the chip, radix 2 (one dependent Fp12 product per level) once it is latency-bound
             const int R = ((size_t)T * nrows > (size_t)n_simd * 64) ? 4 : 2;
             const uint32_t Tout = (T + R - 1) / R;
-            if (R == 2 && (size_t)Tout * nrows <= vm_tree_max && !sw.no_vm)
+            if (R == 2 && (size_t)Tout * nrows <= cfg.pub.vm_tree_max && !cfg.pub.no_vm)
                 hipLaunchKernelGGL(k_vm_fp12_tree, dim3(nblk(Tout, 2 * VM_EPW), (unsigned)nrows), dim3(128), 2 * VM_EPW * VM_F12_SLOTS * sizeof(VmSlot), stream, cur, T, nxt, Tout);
             else
             hipLaunchKernelGGL(k_fp12_tree, dim3(nblk(Tout, 64), (unsigned)nrows), dim3(64), 0, stream, cur, T, nxt, Tout, R);
@@ -1050,7 +952,7 @@ int32_t job_round_partials(Engine* e, ripp_sipp_job* j, Fp12* rows /* [2][68] */
     return rc;
 }
 
-bool fold_g2_table_pays(const Engine* e, size_t half) { return half >= e->fold_tab_min && half > e->gls_split_max && !e->sw.no_fold_tables; }
+bool fold_g2_table_pays(const Engine* e, size_t half) { return half >= e->cfg.pub.fold_tab_min && half > e->cfg.pub.gls_split_max && !e->cfg.pub.no_fold_tables; }
 // ... and the device can hold them: (M + 4 M) affine rows + (M - 1) Jacobian rows per element, M = 4 (fold_g2_table_build).  NOT part of fold_g2_table_pays:
 // that predicate decides whether the vector is x-scaled and must give the same answer every time it is asked within a round; a round whose tables do not
 // fit runs the SAME fold (same halves, same scalar) through the 4-lane split form instead (job_fold), whatever the x-scaling.
@@ -1061,9 +963,9 @@ bool fold_g2_table_fits(const Engine* e, size_t half) {
 // rounds whose G2 fold runs on the x-scaled vector (see ripp_sipp_job::bs): the table folds of a proof driven by sipp_prove_core (every rank of a
 // sharded proof scales ITS shard: z^bs -> z is a homomorphism, so the ranks' corrected partial values multiply to the same group element)
 bool xscale_round(const Engine* e, const ripp_sipp_job* j, size_t half) {
-    if (!j->xs_enabled || e->sw.no_endo || e->sw.no_xscale) return false;
+    if (!j->xs_enabled || e->cfg.pub.no_endo || e->cfg.pub.no_xscale) return false;
     if (fold_g2_table_pays(e, half)) return true;
-    return j->bs_on && half <= e->gls_split_max && 2 * half > e->vm_joint_max && half > e->vm_fold_max;      // stays scaled down to the largest joint-VM round: the return is cheapest on the smallest VM round that walks one group per element
+    return j->bs_on && half <= e->cfg.pub.gls_split_max && 2 * half > e->cfg.pub.vm_joint_max && half > e->cfg.pub.vm_fold_max;      // stays scaled down to the largest joint-VM round: the return is cheapest on the smallest VM round that walks one group per element
 }
 // Round 0 only, single-GPU proofs: enqueue hi2 = 2^64 a_r and 2^32 b_r (normalised) behind the round's pairing products.  The GPU would
 // otherwise idle until the statement hash delivers the first challenge; the fold then needs half the doublings (k_fold_g1_two /
@@ -1074,7 +976,7 @@ bool xscale_round(const Engine* e, const ripp_sipp_job* j, size_t half) {
 // enqueued next on the main stream run beside them instead of after them; the next fold waits for ev_join3.
 int32_t job_precompute_vm(Engine* e, ripp_sipp_job* j, bool side = false) {
     const size_t half = j->len / 2;
-    if (half == 0 || half > e->vm_fold_max || e->sw.no_vm || e->sw.no_precompute) return RIPP_OK;
+    if (half == 0 || half > e->cfg.pub.vm_fold_max || e->cfg.pub.no_vm || e->cfg.pub.no_precompute) return RIPP_OK;
     int32_t rc;
     if ((rc = j->a_pow_h.reserve(half * sizeof(G1J))) || (rc = j->b_pow_h.reserve(half * sizeof(G2J))) || (rc = j->parts1.reserve(2 * half * sizeof(G1J))) || (rc = j->parts2.reserve(8 * half * sizeof(G2J)))) return rc;
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_vm_pow2<Fp>), dim3(nblk(half, 4 * VM_EPW)), dim3(256), 4 * VM_EPW * VmCurve<Fp>::SLOTS * sizeof(VmSlot), e->stream2, j->a.as<G1A>() + half, (uint32_t)half, 64, j->a_pow_h.as<G1J>());
@@ -1094,9 +996,9 @@ int32_t job_precompute_vm(Engine* e, ripp_sipp_job* j, bool side = false) {
 // the same tables (element offset q on G1, none on G2).
 int32_t job_precompute_round0(Engine* e, ripp_sipp_job* j, bool fuse = false) {
     const size_t half = j->len / 2, q = j->len / 4;
-    if (half < ((size_t)1 << 16) || j->digest_ready.load() || j->no_window || e->sw.no_precompute) return RIPP_OK;
+    if (half < ((size_t)1 << 16) || j->digest_ready.load() || j->no_window || e->cfg.pub.no_precompute) return RIPP_OK;
     int32_t rc;
-    bool tables = !e->sw.no_fold_tables;
+    bool tables = !e->cfg.pub.no_fold_tables;
     j->tab_ready = false; j->tab_fused = false;
     // What the device can hold decides the form (Engine::mem_fits; every form folds to the same group elements):
     //   three-quarter tables, 4 multiples (13.6 KB per element of the vector)  >  half-vector tables, FOLD_TAB_M multiples (18.4 KB; the plan without
@@ -1105,7 +1007,7 @@ int32_t job_precompute_round0(Engine* e, ripp_sipp_job* j, bool fuse = false) {
     const size_t tab_held = e->fold_tab1.cap + e->fold_mult.cap + e->fold_tab.cap + e->fold_jac1.cap + e->fold_jac2.cap + e->fix_flags.cap;
     size_t M_half = FOLD_TAB_M;
     if (tables) {
-        const bool want_fuse = fuse && xscale_round(e, j, half) && !e->sw.no_fq && !e->sw.no_fuse && q >= e->fq_min;
+        const bool want_fuse = fuse && xscale_round(e, j, half) && !e->cfg.pub.no_fq && !e->cfg.pub.no_fuse && q >= e->cfg.pub.fq_min;
         if (want_fuse && !e->mem_fits(tab_bytes(4, 3 * q), tab_held)) { fuse = false; e->mem_tier = std::max(e->mem_tier & 7, 1) | (e->mem_tier & 8); }
         if (!(want_fuse && fuse)) {
             if (!e->mem_fits(tab_bytes(M_half, half), tab_held)) { M_half = 4; e->mem_tier = std::max(e->mem_tier & 7, 1) | (e->mem_tier & 8); }
@@ -1113,7 +1015,7 @@ int32_t job_precompute_round0(Engine* e, ripp_sipp_job* j, bool fuse = false) {
         }
         // no room for round-0 tables: the rest of THIS call runs the table-free form as a whole (the RIPP_NO_FOLD_TABLES / no_fold_tables path the 2^17 switch
         // test pins) -- the x-scaled G2 vector and the in-round tables of rounds 1-4 go with them; the switches are re-read at the next C-ABI call
-        if (!tables) e->sw.no_fold_tables = true;
+        if (!tables) e->cfg.pub.no_fold_tables = true;
     }
     if (!tables && !e->mem_fits(half * (sizeof(G1A) + sizeof(G2A) + sizeof(G1J) + sizeof(G2J)), j->a_pow.cap + j->b_pow.cap + j->jac1.cap + j->jac2.cap)) {
         e->mem_tier = 3 | (e->mem_tier & 8);
@@ -1123,11 +1025,11 @@ int32_t job_precompute_round0(Engine* e, ripp_sipp_job* j, bool fuse = false) {
     if (trace_on() && (e->mem_tier & 7)) fprintf(stderr, "[ripp] round-0 tables: memory tier %d (%s)\n", e->mem_tier & 7, tables ? "half-vector tables" : "pre-doubled bases only");
     if ((rc = j->a_pow.reserve(half * sizeof(G1A))) || (rc = j->b_pow.reserve(half * sizeof(G2A))) || (rc = j->jac1.reserve(half * sizeof(G1J))) || (rc = j->jac2.reserve(half * sizeof(G2J)))) return rc;
     if (!tables) {                                              // two-base form: 2^64 a_r, 2^32 b_r
-        if (!e->sw.no_fq) hipLaunchKernelGGL(k_pow2_mul_g1_q, dim3(nblk(half, 256)), dim3(256), 0, e->stream, j->a.as<G1A>() + half, (uint32_t)half, 64, j->jac1.as<G1J>());
+        if (!e->cfg.pub.no_fq) hipLaunchKernelGGL(k_pow2_mul_g1_q, dim3(nblk(half, 256)), dim3(256), 0, e->stream, j->a.as<G1A>() + half, (uint32_t)half, 64, j->jac1.as<G1J>());
         else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pow2_mul<Fp>), dim3(nblk(half, 256)), dim3(256), 0, e->stream, j->a.as<G1A>() + half, (uint32_t)half, 64, j->jac1.as<G1J>());
         HIPCHK(hipGetLastError());
         if ((rc = e->normalize_dev<Fp>(j->jac1.as<G1J>(), half, j->a_pow.as<G1A>()))) return rc;
-        if (!e->sw.no_fq) hipLaunchKernelGGL(k_pow2_mul_g2_q, dim3(nblk(half, 64)), dim3(64), 0, e->stream, j->b.as<G2A>() + half, (uint32_t)half, 32, j->jac2.as<G2J>());
+        if (!e->cfg.pub.no_fq) hipLaunchKernelGGL(k_pow2_mul_g2_q, dim3(nblk(half, 64)), dim3(64), 0, e->stream, j->b.as<G2A>() + half, (uint32_t)half, 32, j->jac2.as<G2J>());
         else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pow2_mul<Fp2>), dim3(nblk(half, 256)), dim3(256), 0, e->stream, j->b.as<G2A>() + half, (uint32_t)half, 32, j->jac2.as<G2J>());
         HIPCHK(hipGetLastError());
         if ((rc = e->normalize_dev<Fp2>(j->jac2.as<G2J>(), half, j->b_pow.as<G2A>()))) return rc;
@@ -1137,7 +1039,7 @@ int32_t job_precompute_round0(Engine* e, ripp_sipp_job* j, bool fuse = false) {
     // table form (kernels.hpp): bases 2^(32 b) P and 2^(16 b) Q, b < 4, and the odd multiples 1, 3, .., 2 M - 1 of each.
     // tab1 / mult2 hold [M b + m][cnt]; row M b is base b itself, written by the doubling chain's normalisation.
     j->tab_on_lo = xscale_round(e, j, half);                    // scaled fold: x multiplies the LOW half
-    fuse = fuse && j->tab_on_lo && !e->sw.no_fq && !e->sw.no_fuse && q >= e->fq_min;
+    fuse = fuse && j->tab_on_lo && !e->cfg.pub.no_fq && !e->cfg.pub.no_fuse && q >= e->cfg.pub.fq_min;
     const size_t M = fuse ? 4 : M_half;
     const size_t cnt = fuse ? 3 * q : half;
     const size_t qstride = (cnt + 63) & ~(size_t)63;
@@ -1152,11 +1054,11 @@ int32_t job_precompute_round0(Engine* e, ripp_sipp_job* j, bool fuse = false) {
     for (int b = 0; b < 4; ++b) {
         G1A* base1 = t1 + M * b * cnt; G2A* base2 = t2 + M * b * cnt;
         if (b > 0) {
-            if (!e->sw.no_fq) hipLaunchKernelGGL(k_pow2_mul_g1_q, dim3(nblk(cnt, 256)), dim3(256), 0, e->stream, base1 - M * cnt, (uint32_t)cnt, 32, sj1);
+            if (!e->cfg.pub.no_fq) hipLaunchKernelGGL(k_pow2_mul_g1_q, dim3(nblk(cnt, 256)), dim3(256), 0, e->stream, base1 - M * cnt, (uint32_t)cnt, 32, sj1);
             else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pow2_mul<Fp>), dim3(nblk(cnt, 256)), dim3(256), 0, e->stream, base1 - M * cnt, (uint32_t)cnt, 32, sj1);
             HIPCHK(hipGetLastError());
             if ((rc = e->normalize_dev<Fp>(sj1, cnt, base1))) return rc;
-            if (!e->sw.no_fq) hipLaunchKernelGGL(k_pow2_mul_g2_q, dim3(nblk(cnt, 64)), dim3(64), 0, e->stream, base2 - M * cnt, (uint32_t)cnt, 16, sj2);
+            if (!e->cfg.pub.no_fq) hipLaunchKernelGGL(k_pow2_mul_g2_q, dim3(nblk(cnt, 64)), dim3(64), 0, e->stream, base2 - M * cnt, (uint32_t)cnt, 16, sj2);
             else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pow2_mul<Fp2>), dim3(nblk(cnt, 256)), dim3(256), 0, e->stream, base2 - M * cnt, (uint32_t)cnt, 16, sj2);
             HIPCHK(hipGetLastError());
             if ((rc = e->normalize_dev<Fp2>(sj2, cnt, base2))) return rc;
@@ -1164,7 +1066,7 @@ int32_t job_precompute_round0(Engine* e, ripp_sipp_job* j, bool fuse = false) {
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_odd_multiples<Fp>), dim3(nblk(cnt, 64)), dim3(64), 0, e->stream, base1, (uint32_t)cnt, (int)M, sj1);
         HIPCHK(hipGetLastError());
         if ((rc = e->normalize_dev<Fp>(sj1, njt, base1 + cnt))) return rc;
-        if (!e->sw.no_fq) {
+        if (!e->cfg.pub.no_fq) {
             hipLaunchKernelGGL(k_odd_multiples_q, dim3(nblk(cnt, 64)), dim3(64), 0, e->stream, base2, (uint32_t)cnt, (int)M, sj2, e->fix_flags.as<uint8_t>());
 #if !defined(RIPP_INLINE_FALLBACK)
             hipLaunchKernelGGL(k_odd_multiples_fix, dim3(FIX_GRID), dim3(64), 0, e->stream, base2, (uint32_t)cnt, (int)M, sj2, e->fix_flags.as<uint8_t>());
@@ -1195,7 +1097,7 @@ int32_t fold_g2_table_build(Engine* e, hipStream_t st, const G2A* hi, size_t hal
     e->tab_owner = nullptr;                                     // whatever round-0 tables were there are overwritten
     G2A* mult = e->fold_mult.as<G2A>();
     HIPCHK(hipMemcpyAsync(mult, hi, half * sizeof(G2A), hipMemcpyDeviceToDevice, st));
-    if (!e->sw.no_fq) {
+    if (!e->cfg.pub.no_fq) {
         hipLaunchKernelGGL(k_odd_multiples_q, dim3(nblk(half, 64)), dim3(64), 0, st, hi, (uint32_t)half, M, e->fold_jac2.as<G2J>(), e->fix_flags.as<uint8_t>());
 #if !defined(RIPP_INLINE_FALLBACK)
         hipLaunchKernelGGL(k_odd_multiples_fix, dim3(FIX_GRID), dim3(64), 0, st, hi, (uint32_t)half, M, e->fold_jac2.as<G2J>(), e->fix_flags.as<uint8_t>());
@@ -1217,7 +1119,7 @@ int32_t fold_g2_table(Engine* e, hipStream_t st, const G2A* hi, const G2A* lo, s
     if (!built && (rc = fold_g2_table_build(e, st, hi, half))) return rc;
     e->g2tab_hi = nullptr;
     if ((rc = jac.reserve(half * sizeof(G2J))) || (rc = e->fix_flags.reserve(4 * half + 16))) return rc;
-    if (!e->sw.no_fq && half >= e->fq_min)
+    if (!e->cfg.pub.no_fq && half >= e->cfg.pub.fq_min)
     {
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fold_g2_tab_q<GlsDigits, 4>), dim3(nblk(half, 64)), dim3(64), 0, st, e->fold_tab.as<uint4>(), qstride, M, lo, (uint32_t)half, gls_wnaf(s, 4), jac.as<G2J>(), e->fix_flags.as<uint8_t>());
 #if !defined(RIPP_INLINE_FALLBACK)
@@ -1236,8 +1138,8 @@ int32_t fold_g2_table(Engine* e, hipStream_t st, const G2A* hi, const G2A* lo, s
 int32_t job_prebuild_g2_tables(Engine* e, ripp_sipp_job* j) {
     const size_t half = j->len / 2;
     e->g2tab_hi = nullptr;
-    if (e->sw.no_prebuild || e->sw.no_endo || half < 1) return RIPP_OK;
-    const bool vm_form = (half <= e->vm_fold_max || half <= e->vm_joint_max) && !e->sw.no_vm;
+    if (e->cfg.pub.no_prebuild || e->cfg.pub.no_endo || half < 1) return RIPP_OK;
+    const bool vm_form = (half <= e->cfg.pub.vm_fold_max || half <= e->cfg.pub.vm_joint_max) && !e->cfg.pub.no_vm;
     if (vm_form || j->pre_ready || j->pre_vm_ready || (j->tab_ready && e->tab_owner == j) || !fold_g2_table_pays(e, half)) return RIPP_OK;
     const bool xs = xscale_round(e, j, half);               // (challenges of SIPP are 128-bit: fits_128 holds)
     if (j->bs_on && !xs) return RIPP_OK;                    // the un-scaling fold takes no tables
@@ -1257,8 +1159,8 @@ int32_t job_fold(Engine* e, ripp_sipp_job* j, const Fr& x, bool allow_vm = true,
     const size_t qstride = (half + 63) & ~(size_t)63;
     if ((rc = e->qtab.reserve(4 * G2A_CHUNKS * qstride * sizeof(uint4))) != RIPP_OK) return rc;
     // G1 half on stream2, G2 half on the main stream (small rounds leave most of the chip idle otherwise)
-    const bool use_vm = allow_vm && half <= e->vm_fold_max && !e->sw.no_vm;
-    const bool mid_vm = allow_vm && !use_vm && half <= e->vm_joint_max && !e->sw.no_vm && !e->sw.no_endo;      // mid-size rounds: one VM group per element
+    const bool use_vm = allow_vm && half <= e->cfg.pub.vm_fold_max && !e->cfg.pub.no_vm;
+    const bool mid_vm = allow_vm && !use_vm && half <= e->cfg.pub.vm_joint_max && !e->cfg.pub.no_vm && !e->cfg.pub.no_endo;      // mid-size rounds: one VM group per element
     if ((rc = e->vm_flag.reserve(sizeof(uint32_t))) != RIPP_OK) return rc;      // (kernel argument of the VM folds; they use the complete addition law and report nothing)
     const bool pre = j->pre_ready && fits_128(x); j->pre_ready = false;      // second bases prepared in the hash window (job_precompute_round0)
     const bool pre_vm = j->pre_vm_ready && fits_128(x) && allow_vm; j->pre_vm_ready = false;   // ... or on the VM during this round's host phase
@@ -1268,7 +1170,7 @@ int32_t job_fold(Engine* e, ripp_sipp_job* j, const Fr& x, bool allow_vm = true,
     const bool tab = j->tab_ready && e->tab_owner == j && fits_128(x); j->tab_ready = false;        // ... with the odd-multiple tables of four bases
     const int tabW = tab_width(j->tab_M);
     const G1A* tab1 = e->fold_tab1.as<G1A>() + (j->tab_fused ? half / 2 : 0);      // three-quarter tables start at A1: a_r is q elements in
-    if (tab && !e->sw.no_fq && half >= e->fq_min)
+    if (tab && !e->cfg.pub.no_fq && half >= e->cfg.pub.fq_min)
         hipLaunchKernelGGL(k_fold_g1_tab_q, dim3(nblk(half, 256)), dim3(256), 0, g1s, tab1, j->tab_cnt, j->tab_M, a, (uint32_t)half, split32_wnaf(x, tabW), j->jac1.as<G1J>());
     else if (tab)
         hipLaunchKernelGGL(k_fold_g1_tab, dim3(nblk(half, 256)), dim3(256), 0, g1s, tab1, j->tab_cnt, j->tab_M, a, (uint32_t)half, split32_wnaf(x, tabW), j->jac1.as<G1J>());
@@ -1280,7 +1182,7 @@ int32_t job_fold(Engine* e, ripp_sipp_job* j, const Fr& x, bool allow_vm = true,
     }
     else if (use_vm || mid_vm)
         hipLaunchKernelGGL(k_vm_fold_g1, dim3(nblk(half, 4 * VM_EPW)), dim3(256), 4 * VM_EPW * VM_G1_SLOTS * sizeof(VmSlot), g1s, a + half, a, (uint32_t)half, naf_digits(x), j->jac1.as<G1J>(), e->vm_flag.as<uint32_t>());
-    else if (!e->sw.no_fq && half >= e->fq_min_g1)
+    else if (!e->cfg.pub.no_fq && half >= e->cfg.pub.fq_min_g1)
         hipLaunchKernelGGL(k_fold_g1_naf_q, dim3(nblk(half, 256)), dim3(256), 0, g1s, a + half, a, (uint32_t)half, naf_digits(x), j->jac1.as<G1J>());
     else
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fold_affine_naf<Fp>), dim3(nblk(half, 256)), dim3(256), 0, g1s, a + half, a, (uint32_t)half, naf_digits(x), j->jac1.as<G1J>());
@@ -1306,7 +1208,7 @@ int32_t job_fold(Engine* e, ripp_sipp_job* j, const Fr& x, bool allow_vm = true,
         for (int t = 0; t < 2; ++t) {
             hipStream_t st2 = t ? e->stream3 : e->stream; const G2A* src = t ? b + half : b; const GlsDigits dg2 = gls_digits(t ? sx_inv : s_inv);
             G2J* parts = e->qtab.as<G2J>() + (size_t)t * 4 * half; uint8_t* flags = e->fix_flags.as<uint8_t>() + (size_t)t * ((4 * half + 15) & ~(size_t)15);
-            if (!e->sw.no_fq) {
+            if (!e->cfg.pub.no_fq) {
                 hipLaunchKernelGGL(k_fold_g2_gls_split_q, dim3(nblk(half, 64), 4), dim3(64), 0, st2, src, (uint32_t)half, dg2, parts, flags);
 #if !defined(RIPP_INLINE_FALLBACK)
                 hipLaunchKernelGGL(k_fold_g2_gls_split_fix, dim3(FIX_GRID), dim3(64), 0, st2, src, (uint32_t)half, dg2, parts, flags);
@@ -1323,7 +1225,7 @@ int32_t job_fold(Engine* e, ripp_sipp_job* j, const Fr& x, bool allow_vm = true,
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_vm_fold_split2<Fp2>), dim3(nblk(half, 4 * VM_EPW), 8), dim3(256), 4 * VM_EPW * VmCurve<Fp2>::SLOTS * sizeof(VmSlot), e->stream, b + half, j->b_pow_h.as<G2J>(), (uint32_t)half, split_digits_g2(x_inv), 4, j->parts2.as<G2J>());
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_vm_combine<Fp2>), dim3(nblk(half, 4 * VM_EPW)), dim3(256), 4 * VM_EPW * VmCurve<Fp2>::SLOTS * sizeof(VmSlot), e->stream, j->parts2.as<G2J>(), 8, b, (uint32_t)half, j->jac2.as<G2J>());
     } else
-    if (tab && !e->sw.no_fq && half >= e->fq_min) {
+    if (tab && !e->cfg.pub.no_fq && half >= e->cfg.pub.fq_min) {
         if ((rc = e->fix_flags.reserve(4 * half + 16))) return rc;
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fold_g2_tab_q<Wnaf16, 16>), dim3(nblk(half, 64)), dim3(64), 0, e->stream, e->fold_tab.as<uint4>(), j->tab2_stride, j->tab_M, g2_lo, (uint32_t)half, gls16_wnaf(g2_s, tabW), j->jac2.as<G2J>(), e->fix_flags.as<uint8_t>());
 #if !defined(RIPP_INLINE_FALLBACK)
@@ -1345,12 +1247,12 @@ int32_t job_fold(Engine* e, ripp_sipp_job* j, const Fr& x, bool allow_vm = true,
         hipLaunchKernelGGL(k_vm_fold_g2_split, dim3(nblk(half, 4 * VM_EPW), 4), dim3(256), 4 * VM_EPW * VM_G2_SLOTS * sizeof(VmSlot), e->stream, b + half, (uint32_t)half, gls_digits(x_inv), e->qtab.as<G2J>(), e->vm_flag.as<uint32_t>());
         hipLaunchKernelGGL(k_vm_combine_g2, dim3(nblk(half, 4 * VM_EPW)), dim3(256), 4 * VM_EPW * VM_G2_SLOTS * sizeof(VmSlot), e->stream, e->qtab.as<G2J>(), b, (uint32_t)half, j->jac2.as<G2J>());
     } else
-    if (e->sw.no_endo) {               // no psi on this build / switch: the 255-bit NAF fold (x^-1 is full width)
+    if (e->cfg.pub.no_endo) {               // no psi on this build / switch: the 255-bit NAF fold (x^-1 is full width)
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fold_affine_naf<Fp2>), dim3(nblk(half, 256)), dim3(256), 0, e->stream, b + half, b, (uint32_t)half, naf_digits(x_inv), j->jac2.as<G2J>());
     } else
-    if (half <= e->gls_split_max || (fold_g2_table_pays(e, half) && !(e->g2tab_hi && e->g2tab_half == half) && !fold_g2_table_fits(e, half) && ((e->mem_tier |= 16), true))) {     // latency-bound round: 4 lanes per element (also: a table round whose tables the device cannot hold, mem_tier + 16)
+    if (half <= e->cfg.pub.gls_split_max || (fold_g2_table_pays(e, half) && !(e->g2tab_hi && e->g2tab_half == half) && !fold_g2_table_fits(e, half) && ((e->mem_tier |= 16), true))) {     // latency-bound round: 4 lanes per element (also: a table round whose tables the device cannot hold, mem_tier + 16)
         if ((rc = e->qtab.reserve(std::max<size_t>(4 * G2A_CHUNKS * qstride * sizeof(uint4), 4 * half * sizeof(G2J)))) != RIPP_OK) return rc;
-        if (!e->sw.no_fq) {
+        if (!e->cfg.pub.no_fq) {
             if ((rc = e->fix_flags.reserve(4 * half + 16))) return rc;
             hipLaunchKernelGGL(k_fold_g2_gls_split_q, dim3(nblk(half, 64), 4), dim3(64), 0, e->stream, g2_hi, (uint32_t)half, gls_digits(g2_s), e->qtab.as<G2J>(), e->fix_flags.as<uint8_t>());
 #if !defined(RIPP_INLINE_FALLBACK)
@@ -1537,7 +1439,7 @@ static int32_t fold_impl(const IN* hi, const IN* lo, size_t half, const ripp_fr*
         Affine<F>*dh, *dl;
         if ((rc = upload<Affine<F>>(e, e->tmpA, hi, half, &dh))) return rc;
         if ((rc = upload<Affine<F>>(e, e->tmpB, lo, half, &dl))) return rc;
-        if (std::is_same<F, Fp2>::value && !e->sw.no_endo) {
+        if (std::is_same<F, Fp2>::value && !e->cfg.pub.no_endo) {
             const size_t qstride = (half + 63) & ~(size_t)63;
             if ((rc = e->qtab.reserve(4 * G2A_CHUNKS * qstride * sizeof(uint4)))) return rc;
             hipLaunchKernelGGL(k_fold_g2_gls, dim3(nblk(half, 64)), dim3(64), 0, e->stream, reinterpret_cast<const G2A*>(dh), reinterpret_cast<const G2A*>(dl), (uint32_t)half,
@@ -1585,14 +1487,14 @@ extern "C++" {
 static std::atomic<int32_t> g_last_slots{1};
 struct DevSlot { Engine* e; size_t off, cnt; };
 static int32_t device_slots(Engine* e, size_t n, size_t min_units, std::vector<DevSlot>* out) {
-    size_t D = e->n_devices_cfg > 1 ? e->n_devices_cfg : 1;
+    size_t D = e->cfg.pub.n_devices > 1 ? e->cfg.pub.n_devices : 1;
     if (min_units && D > n / min_units) D = std::max<size_t>(1, n / min_units);
     out->clear();
     if (D > 1) {
         int count = 0; (void)hipGetDeviceCount(&count);
         for (size_t d = 1; d < D; ++d) {
-            const int phys = e->virtual_devices ? e->device : e->device + (int)d;
-            if (phys >= count) { set_err("n_devices = " + std::to_string(e->n_devices_cfg) + ": device " + std::to_string(phys) + " does not exist (" + std::to_string(count) + " visible)"); (void)hipSetDevice(e->device); return RIPP_ERR_ARG; }
+            const int phys = e->cfg.virtual_devices ? e->device : e->device + (int)d;
+            if (phys >= count) { set_err("n_devices = " + std::to_string(e->cfg.pub.n_devices) + ": device " + std::to_string(phys) + " does not exist (" + std::to_string(count) + " visible)"); (void)hipSetDevice(e->device); return RIPP_ERR_ARG; }
             if (e->peers.size() < d) {
                 Engine* p = new Engine(); const int32_t rc = p->init(phys);
                 (void)hipSetDevice(e->device);
@@ -1725,7 +1627,7 @@ template <class F, bool JAC> static int32_t msm_on(Engine* e, const void* bases,
             HIPCHK(hipStreamWaitEvent(e->stream, e->ev_join, 0));
             return RIPP_OK;
         };
-        if (nl >= 2 && nl * sizeof(Affine<F>) >= e->msm_chunk_min * sizeof(G1A)) {          // (measured: pays from 2^20 G1 / 2^19 G2 bases, i.e. from ~96 MB of them)
+        if (nl >= 2 && nl * sizeof(Affine<F>) >= e->cfg.pub.msm_chunk_min * sizeof(G1A)) {          // (measured: pays from 2^20 G1 / 2^19 G2 bases, i.e. from ~96 MB of them)
             // Large host-slice MSMs in TWO halves on two streams (scratch sets 0 and 1, as the KZG openings use them): the second half of the bases crosses
             // PCIe while the first half's gathered additions run (the bases are 96 / 192 MB at n = 2^20: ~2 / ~4 ms of a 9.5 / 22 ms call in which only the
             // 0.35 ms digit sort was hidden), and the first half's latency-bound bucket stages run beside the second half's additions.  sum = MSM(lo) + MSM(hi).
@@ -1949,7 +1851,7 @@ API void ripp_sipp_job_destroy(ripp_sipp_job* j) {
 static void sipp_job_retire_on(Engine* e, ripp_sipp_job* j) {
     if (!j) return;
     if (j->hash_thread.joinable()) j->hash_thread.join();
-    if (!e->job_cache.full && !e->sw.no_job_cache) {
+    if (!e->job_cache.full && !e->cfg.pub.no_job_cache) {
         DevBuf* d[15]; PinBuf* p[4]; job_buffers(j, d, p);
         bool idle = true; for (PinBuf* b : p) if (b->wait() != RIPP_OK) idle = false;
         if (idle) {
@@ -1967,7 +1869,7 @@ static void sipp_job_retire(ripp_sipp_job* j) {
     {   LOCK;
         if (j->hash_thread.joinable()) j->hash_thread.join();
         Engine* e = g_engine;
-        if (e && !e->job_cache.full && !e->sw.no_job_cache) {
+        if (e && !e->job_cache.full && !e->cfg.pub.no_job_cache) {
             DevBuf* d[15]; PinBuf* p[4]; job_buffers(j, d, p);
             bool idle = true; for (PinBuf* b : p) if (b->wait() != RIPP_OK) idle = false;      // (nothing is in flight after a proof: sipp_prove_core's Quiesce)
             if (idle) {
@@ -2049,7 +1951,7 @@ API int32_t ripp_sipp_job_stats(const ripp_sipp_job* j, ripp_stats* st) { LOCK; 
 // round's six final exponentiations and four GT powers while the device folds and evaluates the round after that.  Same group elements,
 // same proof bytes.
 static bool tail_pipe_ok(const Engine* e, const ripp_sipp_job* j) {
-    return j->len >= 4 && j->len <= e->tail_pipe_max && j->len / 2 <= e->vm_fold_max && 2 * j->len <= e->max_pairs_per_batch && !j->bs_on && j->xs_enabled && !e->sw.no_vm && !e->sw.no_precompute && !e->sw.no_endo;
+    return j->len >= 4 && j->len <= e->cfg.pub.tail_pipe_max && j->len / 2 <= e->cfg.pub.vm_fold_max && 2 * j->len <= e->max_pairs_per_batch && !j->bs_on && j->xs_enabled && !e->cfg.pub.no_vm && !e->cfg.pub.no_precompute && !e->cfg.pub.no_endo;
 }
 // enqueue the eight quarter products of the current vectors: they become round `for_round`'s values
 static int32_t job_tail_enqueue(Engine* e, ripp_sipp_job* j, size_t for_round) {
@@ -2140,16 +2042,16 @@ static HostPool& look_pool() { static HostPool pool(3); return pool; }      // o
 // Returned in EIGHTHS of an item: 8 k + f = the first k items in full and f/8 of the pairs of the next one (the window is a fixed budget; a
 // whole item of round R costs 2^(R-1) n pairs, so the last one is cut to what is left).
 static int look_plan(const Engine* e, size_t n_local, int world, bool window) {
-    if (!window || e->sw.no_precompute || e->sw.no_endo) return 0;
-    if (e->look_eighths >= 0) return std::min(16 * LOOK_MAX_R, e->look_eighths);      // forced plan (ripp_config.look_eighths / RIPP_LOOK_EIGHTHS / RIPP_LOOK_ITEMS)
-    const double share = e->ranks_per_device;                       // ranks sharing this rank's GPU (test rigs: several ranks on one device): their work adds up in the same window
+    if (!window || e->cfg.pub.no_precompute || e->cfg.pub.no_endo) return 0;
+    if (e->cfg.pub.look_eighths >= 0) return std::min(16 * LOOK_MAX_R, e->cfg.pub.look_eighths);      // forced plan (ripp_config.look_eighths / RIPP_LOOK_EIGHTHS / RIPP_LOOK_ITEMS)
+    const double share = e->cfg.ranks_per_device;                       // ranks sharing this rank's GPU (test rigs: several ranks on one device): their work adds up in the same window
     const double nl = (double)n_local * share, n = (double)n_local * world;
     if (n < (double)((size_t)1 << 17)) return 0;                    // small statements: the hash is done long before the GPU is
     // Rates: compiled-in for the FIRST proof of a process (2^20 pairs through lines + products ~80 ms with the carry-free kernels; the statement hash
     // 286 ms at n = 2^20 = 1.17 GB/s of Blake2s in situ with the x86-64 bulk loop, build round 5; 313-317 ms = 1.06-1.12 GB/s before), MEASURED afterwards: sipp_prove_core records this box's hash rate and this device's
     // pairing rate at the end of every large proof that hashed (Engine::cal_*), so the static plan the non-hashing ranks follow is priced with what
     // rank 0's box and GPU really do (boxes differ by +-3 % / +-5 %).  Scaling and the fold tables move with the GPU factor.
-    const double ms_per_pair = (e->cal_ms_per_pair > 0 ? e->cal_ms_per_pair : 6.7e-5) * (1.0 + 0.01 * e->plan_derate_pct);      // (shared G2 chains: 138 ms for the 2^21 pair evaluations of round 0 + (1,l) at n = 2^20; plan_derate_pct: ripp_config, the plan of a slower device)
+    const double ms_per_pair = (e->cal_ms_per_pair > 0 ? e->cal_ms_per_pair : 6.7e-5) * (1.0 + 0.01 * e->cfg.pub.plan_derate_pct);      // (shared G2 chains: 138 ms for the 2^21 pair evaluations of round 0 + (1,l) at n = 2^20; plan_derate_pct: ripp_config, the plan of a slower device)
     const double gpu_f = ms_per_pair / 6.7e-5;
     const double hash_ms = n * 336.0 / (e->cal_hash_bytes_per_ms > 0 ? e->cal_hash_bytes_per_ms : 1.17e6);
     double budget = hash_ms - (nl * (3.2e-5 * gpu_f + ms_per_pair + 5.3e-5 * gpu_f) + 1.0);      // scaling, round 0, fold tables (measured at n = 2^20: 33 + 80 + 55 ms)
@@ -2173,10 +2075,10 @@ static int look_plan(const Engine* e, size_t n_local, int world, bool window) {
 // first_item = 1: item (1,l) was already produced together with round 0 (job_round0_shared).
 static int32_t job_lookahead(Engine* e, ripp_sipp_job* j, int eighths, bool forced, double ms_per_pair, int first_item = 0) {
     if (first_item == 0) j->look.clear();
-    const bool adaptive = !forced && j->hash_total > 0 && !j->no_window && eighths > 0 && !e->look_static;
+    const bool adaptive = !forced && j->hash_total > 0 && !j->no_window && eighths > 0 && !e->cfg.pub.look_static;
     // ranks that do not hash the statement themselves: rank 0 told them when it expects the digest (SippPlanMsg::hash_left_ms, its measured hash rate); they cut or
     // extend the plan it sent by THEIR clock and THEIR measured pairing rate -- a slower or a time-sliced device no longer overruns the window, a faster one uses it
-    const bool by_deadline = !forced && !adaptive && j->look_deadline > 0 && !j->no_window && eighths > 0 && !e->look_static;
+    const bool by_deadline = !forced && !adaptive && j->look_deadline > 0 && !j->no_window && eighths > 0 && !e->cfg.pub.look_static;
     const int items = (adaptive || by_deadline) ? std::min(2 * LOOK_MAX_R, eighths / 8 + 2) : (eighths + 7) / 8;      // adaptive: at most one whole item beyond what the static model expects
     if (items <= 0 || (j->digest_ready.load() && !forced)) return RIPP_OK;      // the hash is already done: nothing to hide the work behind (forced: RIPP_LOOK_ITEMS, tests)
     const double t0 = now_ms();
@@ -2204,7 +2106,7 @@ static int32_t job_lookahead(Engine* e, ripp_sipp_job* j, int eighths, bool forc
             // launch plus the rest of the pipeline (58 % of a pair evaluation).  Measured with recorded peers (profiles/r05_rank0_of_{2,8}_timeline.txt): item
             // (3,l) on 8 192-pair blocks took 59 ms where the rate alone says 37; 11/32 of it on 32 768-pair blocks 62 ms instead of 46 -- the overrun of
             // the two-rank window in build round 4's plan.
-            const double mpp = std::max(ms_per_pair, 5.0e-5) * (1.0 + 0.01 * e->plan_derate_pct), nprod = (double)((size_t)1 << (2 * R));
+            const double mpp = std::max(ms_per_pair, 5.0e-5) * (1.0 + 0.01 * e->cfg.pub.plan_derate_pct), nprod = (double)((size_t)1 << (2 * R));
             auto item_cost = [&](size_t qq) {
                 const size_t per_launch = std::min<size_t>(MAX_PRODUCTS, std::max<size_t>(1, e->max_pairs_per_batch / std::max<size_t>(qq, 1)));
                 const double launches = std::ceil(nprod / (double)per_launch), var = nprod * (double)qq * mpp;
@@ -2377,7 +2279,7 @@ static int32_t sipp_prove_core(Engine* e, ripp_sipp_job* j, const Fp12& val, con
         if (seed_digest) { if (j->hash_thread.joinable()) j->hash_thread.join(); std::memcpy(j->digest, seed_digest, 32); j->digest_ready = true; j->hash_prestarted = false; }
         else job_start_hash(j, val);
     }
-    const bool look_forced = e->look_eighths >= 0;
+    const bool look_forced = e->cfg.pub.look_eighths >= 0;
     int look_items = (rank == 0 || look_forced) ? look_plan(e, j->n_local, world0, window || look_forced) : 0;
     j->no_window = !window; j->look_deadline = 0;
     if (world0 > 1) {
@@ -2401,7 +2303,7 @@ static int32_t sipp_prove_core(Engine* e, ripp_sipp_job* j, const Fp12& val, con
     // RIPP_QUIET_WAITS=1: sleeping instead of spinning waits while this rank hashes.  Measured A/B on four boxes (profiles/r03_quiet_vs_spin_waits.txt):
     // the hash is not faster for it (313-322 vs 312-330 ms) and the wake-up latencies make the adaptive look-ahead overrun the window: 460-470 ms
     // against 458-465 ms with spinning waits.  Off by default.
-    e->quiet_waits = window && e->quiet_waits_cfg;
+    e->quiet_waits = window && e->cfg.pub.quiet_waits;
     j->look_rows[0].blocking = j->look_rows[1].blocking = e->quiet_waits;
     struct XsOff { ripp_sipp_job* j; ~XsOff() { j->xs_enabled = false; } } xs_off{j};
     j->xs_enabled = true; j->seeded = false;
@@ -2466,12 +2368,12 @@ static int32_t sipp_prove_core(Engine* e, ripp_sipp_job* j, const Fp12& val, con
             if (dev[0] && dev[1] && start[0] == 0 && start[1] == 0) {
                 const double tp = now_ms();
                 // round 0 with item (1,l) of the look-ahead planned in full: one evaluation with shared G2 chains (job_round0_shared)
-                shared_r0 = round == 0 && !j->seeded && look_items >= 8 && j->len >= 4 && !e->sw.no_share && !e->sw.no_precompute && (look_forced || !j->digest_ready.load());
+                shared_r0 = round == 0 && !j->seeded && look_items >= 8 && j->len >= 4 && !e->cfg.pub.no_share && !e->cfg.pub.no_precompute && (look_forced || !j->digest_ready.load());
                 if (shared_r0) { if ((rc = job_round0_shared(e, j, rows))) return rc; }
                 else if ((rc = job_round_partials(e, j, rows))) return rc;
                 if (round == 0 && j->len >= ((size_t)1 << 16)) {
                     round0_ms_per_pair = (now_ms() - tp) / (double)(shared_r0 ? 2 * j->len : j->len);      // 2 products x len / 2 pairs (shared: 8 x len / 4)
-                    if (e->ranks_per_device <= 1.0) e->cal_ms_per_pair = round0_ms_per_pair;                 // (a time-sliced device would count its neighbours' work)
+                    if (e->cfg.ranks_per_device <= 1.0) e->cal_ms_per_pair = round0_ms_per_pair;                 // (a time-sliced device would count its neighbours' work)
                 }
             }
             else for (int sd = 0; sd < 2; ++sd) {
@@ -2488,7 +2390,7 @@ static int32_t sipp_prove_core(Engine* e, ripp_sipp_job* j, const Fp12& val, con
             // that item when >= 80 % of it fits (job_lookahead), and a forced full plan measured 409 ms against 416-418 ms for the cautious one on a 289 ms-hash
             // box (profiles/r05_plan_threshold_ab.txt) -- since the x86-64 Blake2s loop the window is ~20 ms shorter than the work that used to fill it.
             const bool plan_fuse = look_forced ? look_items >= 16 : look_items >= 12;
-            if (round == 0 && !j->seeded && (rc = job_precompute_round0(e, j, (plan_fuse || e->sw.fuse_tables) && j->len >= 4))) return rc;
+            if (round == 0 && !j->seeded && (rc = job_precompute_round0(e, j, (plan_fuse || e->cfg.pub.fuse_tables) && j->len >= 4))) return rc;
             if (!j->pre_vm_ready && (rc = job_precompute_vm(e, j))) return rc;                   // small rounds: the same on the VM, during the host phase
             // entry into the pipelined tail -- unless the look-ahead has (round 0: is about to get) both values of the next round
             const bool next_known = round == 0 ? (plan_fuse && j->len >= 4 && (look_forced || !j->digest_ready.load())) : look_full(j, round + 1);
@@ -2545,7 +2447,7 @@ static int32_t sipp_prove_core(Engine* e, ripp_sipp_job* j, const Fp12& val, con
             e->quiet_waits = false;
             // polling workers need cores of their own: forced on (ripp_config.hot_workers = 1) with fewer CPUs than workers they would starve the threads that do the work
             // (measured with recorded peers: rank 0 of 8 confined to 4 cores with polling forced: 349 ms after the digest instead of ~50)
-            host_pool().set_hot(e->hot_workers_cfg ? (e->hot_workers_cfg == 1 && effective_cpus() >= (int)host_pool().size() + 2) : hot_workers_pay(world0));      // the remaining rounds hand 0.1-0.6 ms tasks to the workers every ~2 ms
+            host_pool().set_hot(e->cfg.pub.hot_workers ? (e->cfg.pub.hot_workers == 1 && effective_cpus() >= (int)host_pool().size() + 2) : hot_workers_pay(world0));      // the remaining rounds hand 0.1-0.6 ms tasks to the workers every ~2 ms
         }
         const Fr x = fs::sipp_challenge(j->rng, zl, zr);
         x_prev = x;
@@ -2590,20 +2492,9 @@ static int32_t sipp_prove_core(Engine* e, ripp_sipp_job* j, const Fp12& val, con
 }
 
 // ---- configuration (include/ripp_hip.h: ripp_config) ------------------------------------------------------------------------------------------
-static void config_from_engine(const Engine* e, ripp_config* c) {
-    std::memset(c, 0, sizeof *c); c->struct_size = (uint32_t)sizeof *c;
-    c->no_vm = e->sw.no_vm; c->no_precompute = e->sw.no_precompute; c->no_fold_tables = e->sw.no_fold_tables; c->no_msm_glv = e->sw.no_msm_glv; c->lp_one_lane = e->sw.lp_one_lane;
-    c->no_endo = e->sw.no_endo; c->no_fq = e->sw.no_fq; c->no_xscale = e->sw.no_xscale; c->no_share = e->sw.no_share; c->no_fuse = e->sw.no_fuse; c->fuse_tables = e->sw.fuse_tables; c->scale_no_fq = e->scale_no_fq; c->agg_sequential = e->agg_sequential; c->look_static = e->look_static; c->quiet_waits = e->quiet_waits_cfg;
-    c->look_eighths = e->look_eighths; c->ranks_per_device = (int32_t)e->ranks_per_device; c->msm_c = e->msm_tune.c; c->msm_ch = e->msm_tune.ch; c->msm_gmin = e->msm_tune.gmin; c->no_prebuild = e->sw.no_prebuild;
-    c->vm_lines_max = e->vm_lines_max; c->vm_fold_max = e->vm_fold_max; c->vm_tree_max = e->vm_tree_max; c->gls_split_max = e->gls_split_max; c->msm_vm_merge_max = e->msm_vm_merge_max; c->fold_tab_min = e->fold_tab_min;
-    c->fq_min = e->fq_min; c->lp_fq_min = e->lp_fq_min; c->vm_joint_max = e->vm_joint_max; c->vm_scale_max = e->vm_scale_max; c->tail_pipe_max = e->tail_pipe_max; c->ml_fq_min = e->ml_fq_min; c->fq_min_g1 = e->fq_min_g1; c->msm_lds_sort_min = e->msm_lds_sort_min; c->msm_chunk_min = e->msm_chunk_min;
-    c->mem_cap_bytes = e->mem_cap; c->hot_workers = (uint32_t)e->hot_workers_cfg; c->no_job_cache = e->sw.no_job_cache;
-    c->no_lp_karatsuba = e->sw.no_lp_kara; c->comm_timeout_ms = e->comm_timeout_ms; c->plan_derate_pct = e->plan_derate_pct; c->n_devices = e->n_devices_cfg;
-}
-API int32_t ripp_config_default(ripp_config* cfg) {            // the built-in defaults of this build (needs no device: a throw-away Engine object is never initialised)
+API int32_t ripp_config_default(ripp_config* cfg) {            // the built-in defaults of this build (needs no device)
     if (!cfg) return RIPP_ERR_ARG;
-    Engine tmp; tmp.defaults = Engine::Sizes{tmp.vm_lines_max, tmp.vm_fold_max, tmp.vm_tree_max, tmp.gls_split_max, tmp.msm_vm_merge_max, tmp.fold_tab_min, tmp.fq_min, tmp.lp_fq_min, tmp.vm_joint_max, tmp.vm_scale_max, tmp.tail_pipe_max, tmp.ml_fq_min, tmp.fq_min_g1, tmp.msm_lds_sort_min, tmp.msm_chunk_min};
-    config_from_engine(&tmp, cfg); cfg->look_eighths = -1; cfg->ranks_per_device = 1;
+    *cfg = config_defaults().pub;
     return RIPP_OK;
 }
 API int32_t ripp_configure(const ripp_config* cfg) {
@@ -2616,7 +2507,7 @@ API int32_t ripp_configure(const ripp_config* cfg) {
 API int32_t ripp_config_get(ripp_config* cfg) {                // what the NEXT call runs with: defaults < ripp_configure < environment
     if (!cfg) return RIPP_ERR_ARG;
     LOCK; ENGINE;
-    config_from_engine(e, cfg);
+    *cfg = e->cfg.pub;
     return RIPP_OK;
 }
 
@@ -2640,11 +2531,11 @@ static int32_t sipp_prove_devices(Engine* e, std::vector<DevSlot>& sl, const rip
     Fp12 val; std::memcpy(&val, value, sizeof val);
     struct Out { std::vector<ripp_gt> proof; std::vector<ripp_fr> ch; ripp_stats st; };
     std::vector<Out> outs(D);
-    const bool virt = e->virtual_devices;
+    const bool virt = e->cfg.virtual_devices;
     int32_t rc = run_on_devices(e, sl, [&](Engine* ee, size_t, size_t, int d) -> int32_t {
         t_lcomm = &lc; t_lrank = d;
         struct Unbind { ~Unbind() { t_lcomm = nullptr; t_lrank = 0; } } unbind;
-        if (virt) ee->ranks_per_device = (double)D;                              // the look-ahead plan prices the window per DEVICE
+        if (virt) ee->cfg.ranks_per_device = (double)D;                              // the look-ahead plan prices the window per DEVICE
         std::vector<G1A> sa(nl); std::vector<G2A> sb(nl); std::vector<Fr> sr(nl);      // this rank's residue class (local j <-> global j D + d)
         for (size_t i = 0; i < nl; ++i) { std::memcpy(&sa[i], &a[i * D + (size_t)d], sizeof(G1A)); std::memcpy(&sb[i], &b[i * D + (size_t)d], sizeof(G2A)); std::memcpy(&sr[i], &r[i * D + (size_t)d], sizeof(Fr)); }
         ripp_sipp_job* j = nullptr;
@@ -2674,7 +2565,7 @@ API int32_t ripp_sipp_prove(const ripp_g1a* a, const ripp_g2a* b, const ripp_fr*
     if (!value) return RIPP_ERR_ARG;
     {   // more than one device configured for this process, and a statement worth sharding (>= 2^14 elements per device)?
         LOCK; ENGINE;
-        if (e->n_devices_cfg > 1 && a && b && r && proof) {
+        if (e->cfg.pub.n_devices > 1 && a && b && r && proof) {
             std::vector<DevSlot> sl; int32_t rc = device_slots(e, n, (size_t)1 << 14, &sl); if (rc) return rc;
             size_t D = 1; while (2 * D <= sl.size()) D *= 2;
             g_last_slots = (int32_t)D;

@@ -5,7 +5,7 @@
 //     com_1 = (AFGHO(ck_a[:h], m_a[h:]), <ck_b[h:], m_b[:h]>, <m_a[h:], m_b[:h]>)      com_2 = (AFGHO(ck_a[h:], m_a[:h]), <ck_b[:h], m_b[h:]>, <m_a[:h], m_b[h:]>)
 //     m_a <- c m_a[h:] + m_a[:h]      m_b <- c^-1 m_b[h:] + m_b[:h]      ck_a <- c^-1 ck_a[h:] + ck_a[:h]      ck_b <- c ck_b[h:] + ck_b[:h]
 // The pairing half and the m_a / m_b / ck_a folds are those of tipa_ssm_rounds.  New: the four G1 MSMs of the round.  ck_b and m_a are kept side by side in ONE
-// buffer X = (ck_b | m_a) and the two folds write side by side into the next round's X, so that from vector length e->gipa_mexp_batch_min on the four MSMs are
+// buffer X = (ck_b | m_a) and the two folds write side by side into the next round's X, so that from vector length e->cfg.gipa_mexp_batch_min on the four MSMs are
 // the four rows of one pass of the batched pipeline over X (gipa_mexp.hpp); below it, and under the legacy MSM switches, four single MSMs, two on each side stream.
 extern "C++" {
 struct MexpVecs {
@@ -44,7 +44,7 @@ static int32_t gipa_mexp_rounds(Engine* e, MexpVecs& v, size_t n, ripp_gt* com_g
         G1A* KBn = v.X2.as<G1A>(); G1A* An = KBn + h;                                        // the next round's X = (ck_b | m_a), h elements each
         const G1A* as[2] = {A + h, A}; const G2A* bs[2] = {KA, KA + h};                      // com_1.0 = (m_a_1, ck_a_1), com_2.0 = (m_a_2, ck_a_2)   gipa.rs:209-231
         G1J* const out = v.out.as<G1J>();                                                    // com_1.1, com_1.2, com_2.1, com_2.2
-        const bool batch = !e->msm_batch_legacy() && len >= e->gipa_mexp_batch_min && e->msm_quad_fits(len);
+        const bool batch = !e->msm_batch_legacy() && len >= e->cfg.gipa_mexp_batch_min && e->msm_quad_fits(len);
         const double tp = now_ms();
         if (batch) {            // one digit pass and one sort for the four MSMs, in front of the pairing products on the engine's stream
             if ((rc = e->msm_batch_dev<Fp>(KB, nullptr, S, 4, 2 * len, 0, out, 0, (uint32_t)len))) return rc;

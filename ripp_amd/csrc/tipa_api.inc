@@ -30,7 +30,7 @@ static FoldPre g_tpc_pre;                  // second fold base of the first-tier
 static void vec_caches_release() { g_tipp_cache.release(); g_ssm_cache.release(); g_mexp_cache.release(); g_scal_cache.release(); g_tpc_pre.release(); }
 template <class F> static int32_t fold_precompute(Engine* e, hipStream_t st, const Affine<F>* hi, size_t half, FoldPre& fp) {
     fp.ready = false;
-    if (half == 0 || half > e->vm_fold_max || e->sw.no_vm || e->sw.no_precompute) return RIPP_OK;
+    if (half == 0 || half > e->cfg.pub.vm_fold_max || e->cfg.pub.no_vm || e->cfg.pub.no_precompute) return RIPP_OK;
     constexpr bool g1 = std::is_same<F, Fp>::value;
     int32_t rc; if ((rc = fp.pow_h.reserve(half * sizeof(Jac<F>))) || (rc = fp.parts.reserve((g1 ? 4 : 8) * half * sizeof(Jac<F>)))) return rc;
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_vm_pow2<F>), dim3(nblk(half, 4 * VM_EPW)), dim3(256), 4 * VM_EPW * VmCurve<F>::SLOTS * sizeof(VmSlot), st, hi, (uint32_t)half, g1 ? 64 : 32, fp.pow_h.as<Jac<F>>());
@@ -40,7 +40,7 @@ template <class F> static int32_t fold_precompute(Engine* e, hipStream_t st, con
 // Batched small-round forms: the second bases resp. the folds of up to three vectors of one group in ONE launch sequence on one stream
 // (vm_fold2.hpp: grid.z / grid.y = vector), ending in affine points.
 template <class F> struct FoldReq { const Affine<F>* hi; const Affine<F>* lo; Affine<F>* out; Fr s; FoldPre* fp; };
-static bool fold_batching(const Engine* e, size_t half) { return half != 0 && half <= e->vm_fold_max && !e->sw.no_vm && !e->sw.no_precompute; }
+static bool fold_batching(const Engine* e, size_t half) { return half != 0 && half <= e->cfg.pub.vm_fold_max && !e->cfg.pub.no_vm && !e->cfg.pub.no_precompute; }
 template <class F> static int32_t fold_precompute_batch(Engine* e, hipStream_t st, FoldReq<F>* req, int cnt, size_t half) {
     constexpr bool g1 = std::is_same<F, Fp>::value;
     Pow2Batch<F> pb{};
@@ -72,7 +72,7 @@ template <class F> static int32_t fold_batch_dev(Engine* e, hipStream_t st, Fold
 template <class F> static int32_t fold_dev(Engine* e, hipStream_t st, const Affine<F>* hi, const Affine<F>* lo, size_t half, const Fr& s, DevBuf& jac, DevBuf& qt, Affine<F>* out, FoldPre* fp = nullptr);
 template <> int32_t fold_dev<Fp>(Engine* e, hipStream_t st, const G1A* hi, const G1A* lo, size_t half, const Fr& s, DevBuf& jac, DevBuf&, G1A* out, FoldPre* fp) {
     int32_t rc; if ((rc = jac.reserve(half * sizeof(G1J)))) return rc;
-    if (fp && fp->ready && half <= e->vm_fold_max) {            // four 64-bit digit strings on four lane groups: 64 doublings on the chain instead of 128
+    if (fp && fp->ready && half <= e->cfg.pub.vm_fold_max) {            // four 64-bit digit strings on four lane groups: 64 doublings on the chain instead of 128
         fp->ready = false;
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_vm_fold_split2<Fp>), dim3(nblk(half, 4 * VM_EPW), 4), dim3(256), 4 * VM_EPW * VmCurve<Fp>::SLOTS * sizeof(VmSlot), st, hi, fp->pow_h.as<G1J>(), (uint32_t)half, split_digits_g1_glv(s), 2, fp->parts.as<G1J>());
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_vm_combine<Fp>), dim3(nblk(half, 4 * VM_EPW)), dim3(256), 4 * VM_EPW * VmCurve<Fp>::SLOTS * sizeof(VmSlot), st, fp->parts.as<G1J>(), 4, lo, (uint32_t)half, jac.as<G1J>());
@@ -81,9 +81,9 @@ template <> int32_t fold_dev<Fp>(Engine* e, hipStream_t st, const G1A* hi, const
     }
     if (fp) fp->ready = false;
     // GIPA folds G1 vectors with the full-width challenge c: split it through the GLV endomorphism (128 doublings instead of 255)
-    if (half <= e->vm_fold_max && !e->sw.no_vm)     // latency form (complete additions, nothing to flag)
+    if (half <= e->cfg.pub.vm_fold_max && !e->cfg.pub.no_vm)     // latency form (complete additions, nothing to flag)
         hipLaunchKernelGGL(k_vm_fold_g1_glv, dim3(nblk(half, 4 * VM_EPW)), dim3(256), 4 * VM_EPW * VM_G1_SLOTS * sizeof(VmSlot), st, hi, lo, (uint32_t)half, glv_digits(s), jac.as<G1J>());
-    else if (!e->sw.no_fq)                          // throughput / mid-size rounds: the carry-free twin (fq_curve.hpp)
+    else if (!e->cfg.pub.no_fq)                          // throughput / mid-size rounds: the carry-free twin (fq_curve.hpp)
         hipLaunchKernelGGL(k_fold_g1_glv_q, dim3(nblk(half, 256)), dim3(256), 0, st, hi, lo, (uint32_t)half, glv_digits(s), jac.as<G1J>());
     else
         hipLaunchKernelGGL(k_fold_g1_glv, dim3(nblk(half, 256)), dim3(256), 0, st, hi, lo, (uint32_t)half, glv_digits(s), jac.as<G1J>());
@@ -92,7 +92,7 @@ template <> int32_t fold_dev<Fp>(Engine* e, hipStream_t st, const G1A* hi, const
 }
 template <> int32_t fold_dev<Fp2>(Engine* e, hipStream_t st, const G2A* hi, const G2A* lo, size_t half, const Fr& s, DevBuf& jac, DevBuf& qt, G2A* out, FoldPre* fp) {
     int32_t rc; if ((rc = jac.reserve(half * sizeof(G2J)))) return rc;
-    if (fp && fp->ready && half <= e->vm_fold_max) {            // eight 32-bit digit strings on eight lane groups
+    if (fp && fp->ready && half <= e->cfg.pub.vm_fold_max) {            // eight 32-bit digit strings on eight lane groups
         fp->ready = false;
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_vm_fold_split2<Fp2>), dim3(nblk(half, 4 * VM_EPW), 8), dim3(256), 4 * VM_EPW * VmCurve<Fp2>::SLOTS * sizeof(VmSlot), st, hi, fp->pow_h.as<G2J>(), (uint32_t)half, split_digits_g2(s), 4, fp->parts.as<G2J>());
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_vm_combine<Fp2>), dim3(nblk(half, 4 * VM_EPW)), dim3(256), 4 * VM_EPW * VmCurve<Fp2>::SLOTS * sizeof(VmSlot), st, fp->parts.as<G2J>(), 8, lo, (uint32_t)half, jac.as<G2J>());
@@ -103,11 +103,11 @@ template <> int32_t fold_dev<Fp2>(Engine* e, hipStream_t st, const G2A* hi, cons
     const size_t qstride = (half + 63) & ~(size_t)63;
     const size_t qt_bytes = std::max<size_t>(4 * G2A_CHUNKS * qstride * sizeof(uint4), 4 * half * sizeof(G2J));
     if ((rc = qt.reserve(qt_bytes + 4 * half + 16)) || (rc = e->vm_flag.reserve(sizeof(uint32_t)))) return rc;          // (vm_flag: a vestigial argument of k_vm_fold_g2_split; + one flag byte per lane of the carry-free GLS fold, behind the parts: this call's own scratch, the two G2 folds of a round may run side by side)
-    if (half <= e->vm_fold_max && !e->sw.no_vm) {
+    if (half <= e->cfg.pub.vm_fold_max && !e->cfg.pub.no_vm) {
         hipLaunchKernelGGL(k_vm_fold_g2_split, dim3(nblk(half, 4 * VM_EPW), 4), dim3(256), 4 * VM_EPW * VM_G2_SLOTS * sizeof(VmSlot), st, hi, (uint32_t)half, gls_digits(s), qt.as<G2J>(), e->vm_flag.as<uint32_t>());
         hipLaunchKernelGGL(k_vm_combine_g2, dim3(nblk(half, 4 * VM_EPW)), dim3(256), 4 * VM_EPW * VM_G2_SLOTS * sizeof(VmSlot), st, qt.as<G2J>(), lo, (uint32_t)half, jac.as<G2J>());
-    } else if (half <= e->gls_split_max) {
-        if (!e->sw.no_fq) {
+    } else if (half <= e->cfg.pub.gls_split_max) {
+        if (!e->cfg.pub.no_fq) {
             uint8_t* flags = qt.as<uint8_t>() + qt_bytes;
             hipLaunchKernelGGL(k_fold_g2_gls_split_q, dim3(nblk(half, 64), 4), dim3(64), 0, st, hi, (uint32_t)half, gls_digits(s), qt.as<G2J>(), flags);
 #if !defined(RIPP_INLINE_FALLBACK)
@@ -337,7 +337,7 @@ static int32_t gipa_tipp_core(Engine* e, TippVecs& v, size_t n, ripp_gt* com_ste
             if ((r2 = fold_dev<Fp>(e, e->stream3, KB + split, KB, split, c, v.jac1b, v.qt2, v.KB2.as<G1A>(), &v.pKB))) return r2;       // ck_b <- ck_b_1 * c + ck_b_2
             if ((r2 = fold_dev<Fp2>(e, e->stream, B + split, B, split, c_inv, v.jac2, e->qtab, v.B2.as<G2A>(), &v.pB))) return r2;     // m_b  <- m_b_2 * c_inv + m_b_1
             // the precomputed-base form has its own scratch per vector, so the second G2 fold runs beside the first; the others share e->qtab
-            hipStream_t st_ka = (v.pKA.ready && split <= e->vm_fold_max) ? e->stream5 : e->stream;
+            hipStream_t st_ka = (v.pKA.ready && split <= e->cfg.pub.vm_fold_max) ? e->stream5 : e->stream;
             return fold_dev<Fp2>(e, st_ka, KA + split, KA, split, c_inv_u, v.jac2b, e->qtab, v.KA2.as<G2A>(), &v.pKA);                   // ck_a <- ck_a_2 * c_inv + ck_a_1
         });
         if (rc) return rc;
@@ -786,7 +786,7 @@ static int32_t aggregate_impl(Engine* e, const ripp_srs* srs, const ripp_g1a* a,
         std::memcpy(&out->c_base_a, &ja, sizeof ja); std::memcpy(&out->c_base_b, &hs, sizeof hs); std::memcpy(&out->c_final_ck_a, &jka, sizeof jka);
         std::memcpy(&out->c_opening_a, &oa, sizeof oa); std::memcpy(&out->c_kzg_c, &kc, sizeof kc);
         return RIPP_OK; };
-    Engine* e2 = !e->agg_sequential ? e->aux_engine() : nullptr;
+    Engine* e2 = !e->cfg.pub.agg_sequential ? e->aux_engine() : nullptr;
     // Sharded: both provers exchange through the ONE communicator, their k-th exchanges paired in one all-gather (comm_core.inc: CommMux) -- the order of
     // the collectives is then the same on every rank whatever the threads' timing (build round 4 ran the sub-proofs in sequence for that reason).
     const bool muxed = e2 && sc.world > 1;

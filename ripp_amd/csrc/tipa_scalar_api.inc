@@ -4,7 +4,7 @@
 //     com_1 = (<ck_a[:h], m_a[h:]> in G2, <ck_b[h:], m_b[:h]> in G1, <m_a[h:], m_b[:h]> in Fr)      com_2 = (<ck_a[h:], m_a[:h]>, <ck_b[:h], m_b[h:]>, <m_a[:h], m_b[h:]>)
 //     m_a <- c m_a[h:] + m_a[:h]      m_b <- c^-1 m_b[h:] + m_b[:h]      ck_a <- c^-1 ck_a[h:] + ck_a[:h]      ck_b <- c ck_b[h:] + ck_b[:h]
 // The inner products and the scalar folds are the kernels of the first tier of the transparent commitment (tpc.hpp), the key folds those of the TIPP prover.
-// From key length e->tipa_scalar_cross_min on the two G2 commitments of a round are ONE crossed pass of the batched MSM pipeline in its G2 form
+// From key length e->cfg.tipa_scalar_cross_min on the two G2 commitments of a round are ONE crossed pass of the batched MSM pipeline in its G2 form
 // (tipa_scalar.hpp) and the two G1 commitments one crossed pass of its G1 form (tpc.hpp).  Both passes use the engine's one batch scratch: they are enqueued
 // on the engine's stream one after the other, the G2 pass first.  Below the bound, under the legacy MSM switches and when a pass would not fit one chunk: two
 // single MSMs per group on the two side streams, each scratch reused in stream order.
@@ -35,7 +35,7 @@ static int32_t tipa_scalar_rounds(Engine* e, ScalVecs& v, size_t n, ripp_g2j* co
         const size_t h = len / 2;
         const Fr* MA = v.MA.as<Fr>(); const Fr* MB = v.MB.as<Fr>(); const G2A* KA = v.KA.as<G2A>(); const G1A* KB = v.KB.as<G1A>();
         G2J* const out2 = v.out2.as<G2J>(); G1J* const out1 = v.out1.as<G1J>();              // (com_1.0, com_2.0), (com_1.1, com_2.1)
-        const bool cross = !e->msm_batch_legacy() && len >= e->tipa_scalar_cross_min && e->msm_rows_fit<Fp2>(len, 2) && e->msm_rows_fit<Fp>(len, 2);
+        const bool cross = !e->msm_batch_legacy() && len >= e->cfg.tipa_scalar_cross_min && e->msm_rows_fit<Fp2>(len, 2) && e->msm_rows_fit<Fp>(len, 2);
         const double tp = now_ms();
         if (cross) {
             // rows 0, 1 over ck_a with m_a: <ck_a[:h], m_a[h:]> = com_1.0, <ck_a[h:], m_a[:h]> = com_2.0   (gipa.rs:209-231)

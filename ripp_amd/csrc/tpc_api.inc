@@ -112,7 +112,7 @@ struct FrDot2 {
 // (structured scalars) and e->tpc_k (keys), n elements each, filled on e->stream by the caller (tpc_reserve_first).  ext0 (optional): the extended form
 // of the n keys as they stand before the first round (a resident ripp_tpc_ck has it); after every key fold the batch pipeline rebuilds its own.
 // com_g1[r][2] = (com_1.0, com_2.0), com_fr[r][2] = (com_1.2[0], com_2.2[0]), transcript[r]: ROUND order.
-// A round's two Pedersen commitments are ONE crossed pass of the batched MSM pipeline (tpc.hpp) from key length e->tpc_cross_min on; below it, and under
+// A round's two Pedersen commitments are ONE crossed pass of the batched MSM pipeline (tpc.hpp) from key length e->cfg.tpc_cross_min on; below it, and under
 // the legacy MSM switches, two single MSMs on two streams.
 static int32_t tpc_scalar_rounds(Engine* e, size_t n, const QAff<Fp>* ext0, ripp_g1j* com_g1, ripp_fr* com_fr, ripp_fr* transcript, Fr& ha, Fr& hb) {
     int32_t rc; if ((rc = e->sync())) return rc;
@@ -122,7 +122,7 @@ static int32_t tpc_scalar_rounds(Engine* e, size_t n, const QAff<Fp>* ext0, ripp
     while (len > 1) {
         const size_t h = len / 2;
         const Fr* M = e->tpc_m.as<Fr>(); const Fr* B = e->tpc_b.as<Fr>(); const G1A* K = e->tpc_k.as<G1A>();
-        const bool cross = !e->msm_batch_legacy() && len >= e->tpc_cross_min;
+        const bool cross = !e->msm_batch_legacy() && len >= e->cfg.tpc_cross_min;
         const double tp = now_ms();
         G1J cm[2];
         if (cross) {         // com_1.0 = <ck[:h], m[h:]>, com_2.0 = <ck[h:], m[:h]> as rows 0 and 1 over the whole key vector   gipa.rs:209-231

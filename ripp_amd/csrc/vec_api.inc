@@ -129,7 +129,7 @@ API int32_t ripp_vec_fold(const ripp_vec* hi, const ripp_vec* lo, const ripp_fr*
         if (hi->kind == RIPP_VEC_FR) {
             hipLaunchKernelGGL(k_fold_fr, dim3(nblk(half, 256)), dim3(256), 0, e->stream, vec_ptr<Fr>(hi), vec_ptr<Fr>(lo), (uint32_t)half, sm, vec_ptr<Fr>(v));
             rc = hipGetLastError() == hipSuccess ? e->sync() : RIPP_ERR_DEVICE;
-        } else if (e->sw.no_endo) {                              // builds / switches without the endomorphisms: the plain NAF fold
+        } else if (e->cfg.pub.no_endo) {                              // builds / switches without the endomorphisms: the plain NAF fold
             if (hi->kind == RIPP_VEC_G1) {
                 if (!(rc = e->jacG1.reserve(half * sizeof(G1J)))) {
                     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fold_affine_naf<Fp>), dim3(nblk(half, 256)), dim3(256), 0, e->stream, vec_ptr<G1A>(hi), vec_ptr<G1A>(lo), (uint32_t)half, naf_digits(sm), e->jacG1.as<G1J>());

@@ -645,6 +645,34 @@ def test_configure_api_selects_the_same_forms_as_the_environment(engine, orc):
     assert d.look_eighths == -1 and d.tail_pipe_max == 1 << 11 and d.no_vm == 0 and d.no_precompute == 0
 
 
+def test_config_get_round_trips_every_member(engine):
+    """Every member of ripp_config alone: configure(member=v) then config_get() shows v there and the default everywhere else (csrc/config.hpp resolves
+    the whole struct, no member-by-member copies); the environment overrides a configured value for a u64 row, a flag and a special row; configure()
+    restores the defaults.  No kernel runs.  lp_one_lane reads back 0: the shipped libraries are not A/B builds."""
+    import ctypes
+    import os
+    defaults = engine.config_default().as_dict()
+    try:
+        assert engine.config_get().as_dict() == defaults
+        for name, ctype in engine.config_default()._fields_:
+            if name == "struct_size": continue
+            v = 3 if name == "ranks_per_device" else 1 if ctype is ctypes.c_uint32 and defaults[name] == 0 else defaults[name] + 5      # (1: a selector, or a legal hot_workers / n_devices)
+            assert v != defaults[name]
+            engine.configure(**{name: v})
+            assert engine.config_get().as_dict() == {**defaults, name: 0 if name == "lp_one_lane" else v}, name
+        for var, value, name, configured, want in (("RIPP_FQ_MIN", "4096", "fq_min", 77, 4096), ("RIPP_NO_SHARE", "1", "no_share", 0, 1), ("RIPP_LOOK_ITEMS", "3", "look_eighths", 29, 24)):
+            engine.configure(**{name: configured})
+            assert engine.config_get().as_dict() == {**defaults, name: configured}
+            os.environ[var] = value
+            try:
+                assert engine.config_get().as_dict() == {**defaults, name: want}, var
+            finally:
+                del os.environ[var]
+    finally:
+        engine.configure()
+    assert engine.config_get().as_dict() == defaults
+
+
 @pytest.mark.parametrize("n,eighths", [(4, 16), (16, 48), (256, 48), (1 << 12, 29), (1 << 13, 16), (1 << 14, 45)])
 def test_shared_g2_chains_vs_oracle(engine, orc, n, eighths):
     """Products over the SAME Q vector share one G2 chain in the carry-free stage-1 kernel (fq_miller.hpp: ChainSets, up to four P's per lane):
