@@ -14,7 +14,10 @@
  * are after `deserialize_*` with validation or as outputs of group arithmetic.  The G2 folds, the MSMs and the table folds use the
  * curve endomorphisms (GLV on G1, psi on G2), which equal the corresponding scalar multiples only on those subgroups; a point that is
  * merely on the curve (`new_unchecked`) gives the reference's value only on the G1 side of the SIPP prover, which uses plain arithmetic throughout.
- * The deserialisers of section "wire format" reject such points like arkworks does.
+ * NO compute entry point checks this precondition.  A caller whose points come from outside establishes it in bulk, on the device, with the
+ * calls of section "validation of untrusted points": ripp_validate_g1a / ripp_validate_g2a / ripp_vec_validate for points it already holds,
+ * ripp_de_g1_vec / ripp_de_g2_vec / ripp_de_groth16_proofs for ark-serialize images (SRS and commitment-key files, the proofs handed to
+ * ripp_aggregate_proofs).  The proof deserialisers of section "wire format" reject such points like arkworks does, one element at a time on the host.
  *
  * Status codes: 0 ok, 1 message length mismatch (InnerProductError::MessageLengthInvalid,
  * inner_products/src/lib.rs:65-70), 2 length not a power of two (the asserts at sipp/src/lib.rs:48-53),
@@ -595,6 +598,36 @@ int32_t ripp_de_tipa_ssm_proof(const uint8_t* in, size_t len, int32_t compress, 
 /* single group elements, compressed (48 / 96 bytes) */
 size_t  ripp_ser_g1_compressed(const ripp_g1a* p, uint8_t out[48]);
 size_t  ripp_ser_g2_compressed(const ripp_g2a* p, uint8_t out[96]);
+
+/* ---- validation of untrusted points: what `deserialize_*` with Validate::Yes spends its time in, for whole vectors on the device -------------
+ * One lane per point; the subgroup test is endomorphism-based and EXACT (it accepts a curve point iff [r]P = O):
+ * phi(P) = [x^2 - 1]P on G1 (a 127-step chain), psi(P) = [x]P on G2 (64 steps).  Points of small order and cofactor torsion, which break the
+ * preconditions of the fast group law, are redone with the complete formulas.  Inputs longer than 2^20 points run in chunks through the engine's scratch.
+ * Argument errors (a NULL pointer other than flags, a stride below the image size) return RIPP_ERR_ARG before the device is looked for; n = 0
+ * returns RIPP_OK with *n_bad = 0 and needs no device; otherwise there is no CPU fallback (RIPP_ERR_DEVICE).
+ * OUT OF SCOPE: Jacobian inputs (normalise first); square roots on the device (compressed images take their roots on the host workers);
+ * validation inside ripp_srs_create, ripp_vec_upload_* or any prover -- none of the existing entry points validates. */
+/* GroupAffine::is_on_curve + is_in_correct_subgroup_assuming_on_curve for a whole vector (what `deserialize_*` with Validate::Yes runs per element).
+ * flags (optional, [n]): 0 valid, 1 coordinate not reduced, 2 not on the curve, 3 not in the prime-order subgroup.
+ * *first_bad = n when *n_bad == 0.  RIPP_OK whenever the check ran, whatever it found. */
+int32_t ripp_validate_g1a(const ripp_g1a* p, size_t n, uint8_t* flags, size_t* n_bad, size_t* first_bad);
+int32_t ripp_validate_g2a(const ripp_g2a* p, size_t n, uint8_t* flags, size_t* n_bad, size_t* first_bad);
+int32_t ripp_vec_validate(const ripp_vec* v, uint8_t* flags, size_t* n_bad, size_t* first_bad);   /* G1 / G2 vectors and views; RIPP_ERR_ARG for RIPP_VEC_FR */
+
+/* Vec<G1Affine> / Vec<G2Affine> elements from n ark-serialize 0.4 images, `stride` bytes apart (stride >= image size; no length prefix is read),
+ * compress = 0 / 1.  flag 1 here = malformed image (flag bits, coordinate >= p, what the curve's reader rejects in an infinity image),
+ * flag 2 = not on the curve / x^3 + b has no root.  out[i] = (0, 0) wherever flags[i] != 0.  flags[i] == 0 exactly when the single-element
+ * reader of the proof deserialisers accepts the image, and out[i] is then the point it returns. */
+int32_t ripp_de_g1_vec(const uint8_t* in, size_t stride, size_t n, int32_t compress, ripp_g1a* out, uint8_t* flags, size_t* n_bad, size_t* first_bad);
+int32_t ripp_de_g2_vec(const uint8_t* in, size_t stride, size_t n, int32_t compress, ripp_g2a* out, uint8_t* flags, size_t* n_bad, size_t* first_bad);
+/* n `ark_groth16::Proof` images (A in G1, B in G2, C in G1, in that order: 192 bytes compressed, 384 uncompressed) into the three arrays
+ * ripp_aggregate_proofs takes.  flags (optional): [n][3] for (A, B, C); *n_bad counts PROOFS with a bad member and *first_bad is a PROOF index.
+ * A and C of a chunk of proofs share one G1 launch. */
+int32_t ripp_de_groth16_proofs(const uint8_t* in, size_t stride, size_t n, int32_t compress, ripp_g1a* a, ripp_g2a* b, ripp_g1a* c,
+                               uint8_t* flags, size_t* n_bad, size_t* first_bad);
+/* test hook: points per device launch of the six calls above (0 restores the default, 2^20); returns the previous value.  It lets a test put
+ * chunk seams into a vector of a few hundred points; it is not a tuning knob. */
+size_t  ripp_validate_set_chunk(size_t chunk);
 
 /* ---- host-side helpers (no device needed): what the host code around the kernels computes ---------------- */
 /* BLAKE2s-256 (RFC 7693; `blake2::Blake2s` of sipp/src/lib.rs:230) of a host buffer: the implementation the statement hash runs, exposed for tests */

@@ -18,7 +18,8 @@ __all__ = ["InnerProductError", "DeviceError", "Vec", "PairingInnerProduct", "Mu
            "PedersenCommitmentG2", "SIPP", "SippJob", "GIPA_TIPP", "GIPA_MEXP", "SRS", "TIPA_TIPP", "TIPA_MEXP", "TIPA_SCALAR", "TIPAWithSSM", "aggregate_proofs", "aggregate_proofs_sharded", "gipa_tipp_prove_sharded", "verify_aggregate_proof", "AggregateProof", "ser_tipa_tipp_proof", "de_tipa_tipp_proof", "ser_tipa_ssm_proof", "de_tipa_ssm_proof", "ser_g1_compressed", "ser_g2_compressed", "product_of_pairings", "product_of_pairings_with_coeffs",
            "normalize_batch_g1", "normalize_batch_g2", "fold_g1_affine", "fold_g2_affine", "fold_g1", "fold_g2",
            "scale_g1_affine", "synth_g1", "synth_g2", "synth_fr", "init", "device_count", "final_exponentiation",
-           "ser_gt", "ser_g1", "ser_g2", "ser_fr", "sipp_seed_digest", "gt_mul", "statement_hash_times", "configure", "config_default", "config_get", "release_scratch", "device_bytes"]
+           "ser_gt", "ser_g1", "ser_g2", "ser_fr", "sipp_seed_digest", "gt_mul", "statement_hash_times", "configure", "config_default", "config_get", "release_scratch", "device_bytes",
+           "validate_g1", "validate_g2", "vec_validate", "deserialize_g1_vec", "deserialize_g2_vec", "deserialize_groth16_proofs"]
 
 
 class InnerProductError(Exception):
@@ -802,6 +803,70 @@ def aggregate_proofs(ip_srs, a, b, c):
     pf = AggregateProof(len(a)); st = RippStats()
     _check(lib().ripp_aggregate_proofs(ip_srs._h, _p(a), _p(b), _p(c), ctypes.c_size_t(len(a)), pf.ref(), ctypes.byref(st)))
     return pf, st.as_dict()
+
+
+# ---- validation of untrusted points (include/ripp_hip.h: "validation of untrusted points"): curve equation and prime-order subgroup, on the device ----
+def _validated(call, n, group=1):
+    """call(flags pointer, n_bad pointer, first_bad pointer) -> (flags uint8 (n,) or (n, group), n_bad, first_bad)"""
+    flags = np.zeros((n, group) if group > 1 else (n,), dtype=np.uint8)
+    n_bad, first_bad = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    _check(call(flags.ctypes.data_as(ctypes.c_void_p), ctypes.byref(n_bad), ctypes.byref(first_bad)))
+    return flags, int(n_bad.value), int(first_bad.value)
+
+
+def validate_g1(points):
+    """points (n,12) G1Affine -> (flags, n_bad, first_bad); flags: 0 valid, 1 coordinate not reduced, 2 not on the curve, 3 not in the
+    prime-order subgroup (`deserialize_*` with Validate::Yes, for the whole vector); first_bad == n when nothing is bad."""
+    a = _c(points, 12)
+    return _validated(lambda f, nb, fb: lib().ripp_validate_g1a(_p(a), ctypes.c_size_t(len(a)), f, nb, fb), len(a))
+
+
+def validate_g2(points):
+    """points (n,24) G2Affine -> (flags, n_bad, first_bad), as validate_g1"""
+    a = _c(points, 24)
+    return _validated(lambda f, nb, fb: lib().ripp_validate_g2a(_p(a), ctypes.c_size_t(len(a)), f, nb, fb), len(a))
+
+
+def vec_validate(vec):
+    """a resident G1 / G2 Vec or view -> (flags, n_bad, first_bad); first_bad is relative to the view"""
+    return _validated(lambda f, nb, fb: lib().ripp_vec_validate(vec._h, f, nb, fb), len(vec))
+
+
+def _images(data, n, size, stride):
+    buf = np.frombuffer(bytes(data), dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+    stride = size if stride is None else int(stride)
+    if n is None: n = 0 if buf.size < size else (buf.size - size) // max(stride, 1) + 1
+    if n and stride >= size and buf.size < (n - 1) * stride + size: raise ValueError(f"{buf.size} bytes do not hold {n} images of {size} bytes, {stride} apart")
+    return (buf if buf.size else np.zeros(1, dtype=np.uint8)), n, stride
+
+
+def _de_vec(fn, cols, size, data, compress, n, stride):
+    buf, n, stride = _images(data, n, size, stride)
+    out = np.zeros((n, cols), dtype=np.uint64)
+    flags, n_bad, first_bad = _validated(lambda f, nb, fb: fn(_p(buf), ctypes.c_size_t(stride), ctypes.c_size_t(n), ctypes.c_int32(1 if compress else 0), _p(out), f, nb, fb), n)
+    return out, flags, n_bad, first_bad
+
+
+def deserialize_g1_vec(data, compress=True, n=None, stride=None):
+    """n ark-serialize images of G1Affine, `stride` bytes apart (default: back to back, n from the length; no length prefix is read)
+    -> (points (n,12), flags, n_bad, first_bad).  flags: 1 malformed image, 2 not on the curve / no root, 3 not in the subgroup; a flagged
+    element comes back as (0, 0).  Parsed on the library's host workers, subgroup-tested on the device."""
+    return _de_vec(lib().ripp_de_g1_vec, 12, 48 if compress else 96, data, compress, n, stride)
+
+
+def deserialize_g2_vec(data, compress=True, n=None, stride=None):
+    """as deserialize_g1_vec for G2Affine -> (points (n,24), flags, n_bad, first_bad)"""
+    return _de_vec(lib().ripp_de_g2_vec, 24, 96 if compress else 192, data, compress, n, stride)
+
+
+def deserialize_groth16_proofs(data, compress=True, n=None, stride=None):
+    """n `ark_groth16::Proof` images (A, B, C) -> (a (n,12), b (n,24), c (n,12), flags (n,3), n_bad, first_bad): the three arrays
+    aggregate_proofs takes.  n_bad counts proofs with a bad member, first_bad is a proof index."""
+    buf, n, stride = _images(data, n, 192 if compress else 384, stride)
+    a, b, c = np.zeros((n, 12), dtype=np.uint64), np.zeros((n, 24), dtype=np.uint64), np.zeros((n, 12), dtype=np.uint64)
+    flags, n_bad, first_bad = _validated(lambda f, nb, fb: lib().ripp_de_groth16_proofs(_p(buf), ctypes.c_size_t(stride), ctypes.c_size_t(n), ctypes.c_int32(1 if compress else 0),
+                                                                                      _p(a), _p(b), _p(c), f, nb, fb), n, 3)
+    return a, b, c, flags, n_bad, first_bad
 
 
 def aggregate_proofs_sharded(ip_srs, a_shard, b_shard, c_shard):

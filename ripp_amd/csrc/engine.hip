@@ -35,6 +35,7 @@
 #include "vm.hpp"
 #include "fq_curve.hpp"
 #include "fq_curve2.hpp"
+#include "fq_validate.hpp"
 #include "fq_line_products.hpp"
 #include "fq_line_products_k.hpp"
 #include "fq_miller.hpp"
@@ -2632,6 +2633,8 @@ API int32_t ripp_sipp_challenge(uint8_t seed[32], const ripp_gt* z_l, const ripp
 }
 
 #include "vec_api.inc"       // device-resident vectors (ripp_vec_*)
+
+#include "validate_api.inc"  // bulk validation of untrusted points (curve equation, prime-order subgroup) and the byte readers that end in it
 
 #include "poly_commit_api.inc"      // KZG / bivariate / univariate polynomial commitments on a resident SRS handle, the batched shared-base MSM
 

@@ -164,66 +164,72 @@ template <class F> bool in_subgroup(const Affine<F>& p) {
     uint32_t r[8]; for (int i = 0; i < 8; ++i) r[i] = FrParams::mod(i);
     return is_inf(scalar_mul_bits(p, r, 255));                     // (255 bits cover r on both curves: leading zero bits only double the identity)
 }
-// deserialize_{un,}compressed with Validate::Yes: flags, range, curve equation, prime-order subgroup
+// deserialize_{un,}compressed with Validate::Yes: flags, range, curve equation, prime-order subgroup.  parse_g1 / parse_g2 do everything but the subgroup
+// test and say WHY an image is rejected (the bulk readers of validate_api.inc parse with them on the host workers and test the subgroup on the device);
+// get_g1 / get_g2 -- the single-element readers of the proof deserialisers -- add the subgroup test on the host.
+enum { PARSE_OK = 0, PARSE_FORMAT = 1 /* flag bits, a coordinate >= p, a non-canonical infinity image */, PARSE_CURVE = 2 /* not on the curve / x^3 + b has no root */ };
 #if defined(RIPP_BLS12_377)
 // generic SWFlags layout: the flags sit in the LAST byte of the image (of x when compressed, of y otherwise); `both flags set` is invalid
 inline bool get_fp_le_flags(const uint8_t* in, Fp& out, uint8_t& flags) {
     uint8_t b[48]; std::memcpy(b, in, 48); flags = b[47] & 0xC0; b[47] &= 0x3F;
     return get_fp_le(b, out);
 }
-inline bool get_g1(const uint8_t* in, bool compress, G1A& p) {
+inline int parse_g1(const uint8_t* in, bool compress, G1A& p) {
     uint8_t fl; Fp y;
-    if (compress) { if (!get_fp_le_flags(in, p.x, fl)) return false; }
-    else { if (!get_fp_le(in, p.x)) return false; if (!get_fp_le_flags(in + 48, y, fl)) return false; }
-    if (fl == 0xC0) return false;
-    if (fl & 0x40) { p = aff_inf<Fp>(); return true; }            // arkworks returns zero whatever the coordinate bytes hold
+    if (compress) { if (!get_fp_le_flags(in, p.x, fl)) return PARSE_FORMAT; }
+    else { if (!get_fp_le(in, p.x)) return PARSE_FORMAT; if (!get_fp_le_flags(in + 48, y, fl)) return PARSE_FORMAT; }
+    if (fl == 0xC0) return PARSE_FORMAT;
+    if (fl & 0x40) { p = aff_inf<Fp>(); return PARSE_OK; }            // arkworks returns zero whatever the coordinate bytes hold
     if (compress) {
-        if (!fp_sqrt(add(mul(mul(p.x, p.x), p.x), curve_b((const Fp*)nullptr)), y)) return false;
+        if (!fp_sqrt(add(mul(mul(p.x, p.x), p.x), curve_b((const Fp*)nullptr)), y)) return PARSE_CURVE;
         if (lex_largest(y) != ((fl & 0x80) != 0)) y = neg(y);
         p.y = y;
-    } else { p.y = y; if (!on_curve(p)) return false; }
-    return in_subgroup(p);
+    } else { p.y = y; if (!on_curve(p)) return PARSE_CURVE; }
+    return PARSE_OK;
 }
-inline bool get_g2(const uint8_t* in, bool compress, G2A& p) {
+inline int parse_g2(const uint8_t* in, bool compress, G2A& p) {
     uint8_t fl, f0; Fp2 y;
-    if (compress) { if (!get_fp_le(in, p.x.c0) || !get_fp_le_flags(in + 48, p.x.c1, fl)) return false; }
-    else { if (!get_fp_le(in, p.x.c0) || !get_fp_le(in + 48, p.x.c1) || !get_fp_le(in + 96, y.c0) || !get_fp_le_flags(in + 144, y.c1, fl)) return false; }
+    if (compress) { if (!get_fp_le(in, p.x.c0) || !get_fp_le_flags(in + 48, p.x.c1, fl)) return PARSE_FORMAT; }
+    else { if (!get_fp_le(in, p.x.c0) || !get_fp_le(in + 48, p.x.c1) || !get_fp_le(in + 96, y.c0) || !get_fp_le_flags(in + 144, y.c1, fl)) return PARSE_FORMAT; }
     (void)f0;
-    if (fl == 0xC0) return false;
-    if (fl & 0x40) { p = aff_inf<Fp2>(); return true; }
+    if (fl == 0xC0) return PARSE_FORMAT;
+    if (fl & 0x40) { p = aff_inf<Fp2>(); return PARSE_OK; }
     if (compress) {
-        if (!fp2_sqrt(add(mul(sqr(p.x), p.x), curve_b((const Fp2*)nullptr)), y)) return false;
+        if (!fp2_sqrt(add(mul(sqr(p.x), p.x), curve_b((const Fp2*)nullptr)), y)) return PARSE_CURVE;
         if (lex_largest(y) != ((fl & 0x80) != 0)) y = neg(y);
         p.y = y;
-    } else { p.y = y; if (!on_curve(p)) return false; }
-    return in_subgroup(p);
+    } else { p.y = y; if (!on_curve(p)) return PARSE_CURVE; }
+    return PARSE_OK;
 }
 #else
-inline bool get_g1(const uint8_t* in, bool compress, G1A& p) {
+inline int parse_g1(const uint8_t* in, bool compress, G1A& p) {
     const uint8_t fl = in[0];
-    if (((fl & 0x80) != 0) != compress) return false;
-    if (fl & 0x40) { for (size_t i = 0; i < g1_size(compress); ++i) if ((i ? in[i] : (in[0] & 0x1f)) != 0) return false; if (!compress && (fl & 0x20)) return false; p = aff_inf<Fp>(); return true; }
-    if (!get_fp_be(in, p.x, true)) return false;
+    if (((fl & 0x80) != 0) != compress) return PARSE_FORMAT;
+    if (fl & 0x40) { for (size_t i = 0; i < g1_size(compress); ++i) if ((i ? in[i] : (in[0] & 0x1f)) != 0) return PARSE_FORMAT; if (!compress && (fl & 0x20)) return PARSE_FORMAT; p = aff_inf<Fp>(); return PARSE_OK; }
+    if (!get_fp_be(in, p.x, true)) return PARSE_FORMAT;
     if (compress) {
-        Fp y; if (!fp_sqrt(add(mul(mul(p.x, p.x), p.x), curve_b((const Fp*)nullptr)), y)) return false;
+        Fp y; if (!fp_sqrt(add(mul(mul(p.x, p.x), p.x), curve_b((const Fp*)nullptr)), y)) return PARSE_CURVE;
         if (lex_largest(y) != ((fl & 0x20) != 0)) y = neg(y);
         p.y = y;
-    } else { if (fl & 0x20) return false; if (!get_fp_be(in + 48, p.y, false)) return false; if (!on_curve(p)) return false; }
-    return in_subgroup(p);
+    } else { if (fl & 0x20) return PARSE_FORMAT; if (!get_fp_be(in + 48, p.y, false)) return PARSE_FORMAT; if (!on_curve(p)) return PARSE_CURVE; }
+    return PARSE_OK;
 }
-inline bool get_g2(const uint8_t* in, bool compress, G2A& p) {
+inline int parse_g2(const uint8_t* in, bool compress, G2A& p) {
     const uint8_t fl = in[0];
-    if (((fl & 0x80) != 0) != compress) return false;
-    if (fl & 0x40) { for (size_t i = 0; i < g2_size(compress); ++i) if ((i ? in[i] : (in[0] & 0x1f)) != 0) return false; if (!compress && (fl & 0x20)) return false; p = aff_inf<Fp2>(); return true; }
-    if (!get_fp_be(in, p.x.c1, true) || !get_fp_be(in + 48, p.x.c0, false)) return false;
+    if (((fl & 0x80) != 0) != compress) return PARSE_FORMAT;
+    if (fl & 0x40) { for (size_t i = 0; i < g2_size(compress); ++i) if ((i ? in[i] : (in[0] & 0x1f)) != 0) return PARSE_FORMAT; if (!compress && (fl & 0x20)) return PARSE_FORMAT; p = aff_inf<Fp2>(); return PARSE_OK; }
+    if (!get_fp_be(in, p.x.c1, true) || !get_fp_be(in + 48, p.x.c0, false)) return PARSE_FORMAT;
     if (compress) {
-        Fp2 y; if (!fp2_sqrt(add(mul(sqr(p.x), p.x), curve_b((const Fp2*)nullptr)), y)) return false;
+        Fp2 y; if (!fp2_sqrt(add(mul(sqr(p.x), p.x), curve_b((const Fp2*)nullptr)), y)) return PARSE_CURVE;
         if (lex_largest(y) != ((fl & 0x20) != 0)) y = neg(y);
         p.y = y;
-    } else { if (fl & 0x20) return false; if (!get_fp_be(in + 96, p.y.c1, false) || !get_fp_be(in + 144, p.y.c0, false)) return false; if (!on_curve(p)) return false; }
-    return in_subgroup(p);
+    } else { if (fl & 0x20) return PARSE_FORMAT; if (!get_fp_be(in + 96, p.y.c1, false) || !get_fp_be(in + 144, p.y.c0, false)) return PARSE_FORMAT; if (!on_curve(p)) return PARSE_CURVE; }
+    return PARSE_OK;
 }
 #endif
+
+inline bool get_g1(const uint8_t* in, bool compress, G1A& p) { return parse_g1(in, compress, p) == PARSE_OK && (is_inf(p) || in_subgroup(p)); }
+inline bool get_g2(const uint8_t* in, bool compress, G2A& p) { return parse_g2(in, compress, p) == PARSE_OK && (is_inf(p) || in_subgroup(p)); }
 
 struct Writer {
     std::vector<uint8_t> b;

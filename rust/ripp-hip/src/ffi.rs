@@ -258,6 +258,13 @@ extern "C" {
     pub fn ripp_de_tipa_ssm_proof(in_: *const u8, len: usize, compress: i32, max_rounds: usize, rounds: *mut usize, com_gt: *mut RippGt, com_g1: *mut RippG1J, base_a: *mut RippG1J, base_b: *mut RippFr, final_ck_a: *mut RippG2J, opening_a: *mut RippG2J) -> i32;
     pub fn ripp_ser_g1_compressed(p: *const RippG1A, out: *mut u8) -> usize;
     pub fn ripp_ser_g2_compressed(p: *const RippG2A, out: *mut u8) -> usize;
+    pub fn ripp_validate_g1a(p: *const RippG1A, n: usize, flags: *mut u8, n_bad: *mut usize, first_bad: *mut usize) -> i32;
+    pub fn ripp_validate_g2a(p: *const RippG2A, n: usize, flags: *mut u8, n_bad: *mut usize, first_bad: *mut usize) -> i32;
+    pub fn ripp_vec_validate(v: *const RippVec, flags: *mut u8, n_bad: *mut usize, first_bad: *mut usize) -> i32;
+    pub fn ripp_de_g1_vec(in_: *const u8, stride: usize, n: usize, compress: i32, out: *mut RippG1A, flags: *mut u8, n_bad: *mut usize, first_bad: *mut usize) -> i32;
+    pub fn ripp_de_g2_vec(in_: *const u8, stride: usize, n: usize, compress: i32, out: *mut RippG2A, flags: *mut u8, n_bad: *mut usize, first_bad: *mut usize) -> i32;
+    pub fn ripp_de_groth16_proofs(in_: *const u8, stride: usize, n: usize, compress: i32, a: *mut RippG1A, b: *mut RippG2A, c: *mut RippG1A, flags: *mut u8, n_bad: *mut usize, first_bad: *mut usize) -> i32;
+    pub fn ripp_validate_set_chunk(chunk: usize) -> usize;
     pub fn ripp_blake2s(in_: *const u8, len: usize, out: *mut u8) -> i32;
     pub fn ripp_final_exp(miller_value: *const RippGt, out: *mut RippGt) -> i32;
     pub fn ripp_miller_combine(step_products: *const RippGt, out: *mut RippGt) -> i32;

@@ -113,6 +113,24 @@ impl TIPACompatibleSetup for HipAFGHOCommitmentG2 {}
 impl TIPACompatibleSetup for HipPedersenCommitmentG1 {}
 impl TIPACompatibleSetup for HipPedersenCommitmentG2 {}
 
+// ---- validation of untrusted points (include/ripp_hip.h: "validation of untrusted points") ---------------------------------------
+/// `GroupAffine::is_on_curve` + `is_in_correct_subgroup_assuming_on_curve` for a whole slice, on the device: what `deserialize_*` with
+/// `Validate::Yes` runs per element.  For points built with `new_unchecked` or read with `Validate::No`; every other entry point of this
+/// crate assumes points of G1 / G2 proper and checks nothing.  `Ok(Err(i))`: element `i` is the first that is not a valid point.
+pub fn hip_validate_g1(points: &[G1Affine]) -> Result<Result<(), usize>, Error> {
+    let l: Vec<RippG1A> = points.iter().map(g1a).collect();
+    let (mut n_bad, mut first_bad) = (0usize, 0usize);
+    status(unsafe { ripp_validate_g1a(l.as_ptr(), l.len(), core::ptr::null_mut(), &mut n_bad, &mut first_bad) }, 0, 0)?;
+    Ok(if n_bad == 0 { Ok(()) } else { Err(first_bad) })
+}
+/// The same for `&[G2Affine]`.
+pub fn hip_validate_g2(points: &[G2Affine]) -> Result<Result<(), usize>, Error> {
+    let l: Vec<RippG2A> = points.iter().map(g2a).collect();
+    let (mut n_bad, mut first_bad) = (0usize, 0usize);
+    status(unsafe { ripp_validate_g2a(l.as_ptr(), l.len(), core::ptr::null_mut(), &mut n_bad, &mut first_bad) }, 0, 0)?;
+    Ok(if n_bad == 0 { Ok(()) } else { Err(first_bad) })
+}
+
 // ---- sipp crate counterparts (sipp/src/lib.rs) ---------------------------------------------------------------------------------
 /// `product_of_pairings(a, b)` (sipp/src/lib.rs:219-224)
 pub fn hip_product_of_pairings(a: &[G1Affine], b: &[G2Affine]) -> Result<PairingOutput<Bls12_381>, Error> {
