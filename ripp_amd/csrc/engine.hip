@@ -329,6 +329,7 @@ struct Engine {
     // run-time configuration (config.hpp): resolved ONCE per C-ABI call (get_engine), never inside round loops
     Config cfg = config_defaults();
     void refresh_switches() { cfg = config_resolve(g_cfg_set ? &g_cfg : nullptr); }
+    static constexpr const char* MSM_TUNE_RANGE = "msm: msm_c (RIPP_MSM_C) must be 0 or 4..13, msm_ch (RIPP_MSM_CH) and msm_gmin (RIPP_MSM_GMIN) 0 or 1..65536";
     MsmTune msm_tune() const { return {cfg.pub.msm_c, cfg.pub.msm_ch, cfg.pub.msm_gmin}; }
     double cal_ms_per_pair = 0, cal_hash_bytes_per_ms = 0;        // look_plan's rates as measured by the last large proof of this process (0: not yet)
 
@@ -448,6 +449,7 @@ struct Engine {
     // bases_arrive (optional): called once the digit sort -- which reads only the scalars -- is enqueued; it brings the bases to the device on another
     // stream and makes `st` wait for them, so that a host-slice MSM uploads its bases beside the sort instead of in front of it.
     template <class F> int32_t msm_launch(MsmScratch& ms, hipStream_t st, const Affine<F>* bases, const Fr* scalars, size_t n, const std::function<int32_t()>* bases_arrive = nullptr) {
+        if (!msm_tune_ok(msm_tune())) { set_err(MSM_TUNE_RANGE); return RIPP_ERR_ARG; }                 // before any allocation or launch (msm.hpp msm_tune_ok)
         if (!ms.host_out) HIPCHK(hipHostMalloc(&ms.host_out, sizeof(G2J), hipHostMallocDefault));
         if (n == 0) { *reinterpret_cast<Jac<F>*>(ms.host_out) = jac_inf<F>(); return bases_arrive ? (*bases_arrive)() : RIPP_OK; }
         const bool no_glv = cfg.pub.no_msm_glv;
@@ -557,6 +559,7 @@ struct Engine {
     bool msm_batch_legacy() const { return cfg.no_msm_batch || cfg.pub.no_msm_glv || cfg.pub.no_fq || cfg.pub.no_vm; }
     // `rows` rows over `cols` bases run as ONE chunk: grid.y, the 32-bit slot index of the fix-up kernels and the memory budget
     template <class F> bool msm_rows_fit(size_t cols, size_t rows) {
+        if (!msm_tune_ok(msm_tune())) { set_err(MSM_TUNE_RANGE); return false; }                          // (the caller's per-row msm_launch calls return RIPP_ERR_ARG)
         const MsmPlan p = msm_plan_batch(cols, msm_batch_split<F>(), rows, msm_tune());
         const size_t max_slots = (size_t)p.n / p.ch + std::min<size_t>(p.nb, p.n) + 1;
         if (rows * (size_t)p.nwin > 65535 || rows * (size_t)p.nwin * max_slots >= ((size_t)1 << 32)) return false;
@@ -569,6 +572,7 @@ struct Engine {
         constexpr bool g1 = std::is_same<F, Fp>::value;
         constexpr int split = msm_batch_split<F>();
         msm_batch_chunks = 0;
+        if (!msm_tune_ok(msm_tune())) { set_err(MSM_TUNE_RANGE); return RIPP_ERR_ARG; }
         if (rows == 0) return RIPP_OK;
         hipStream_t st = stream; int32_t rc;
         if (!g1 && !cross_h) { set_err("msm_batch_dev: the G2 pipeline has the crossed form only"); return RIPP_ERR_ARG; }

@@ -40,6 +40,14 @@ constexpr int MSM_SEG_FAN = 4;       // segment sums added per lane in k_msm_seg
 struct MsmPlan { int c, nwin; uint32_t nb; uint32_t n; uint32_t ch, seg; uint32_t nreal, gmin; };   // ch: max terms per slot, seg: buckets per segment lane
 
 struct MsmTune { int c = 0; uint32_t ch = 0, gmin = 0; };      // 0 = the plan's own choice (RIPP_MSM_C / RIPP_MSM_CH / RIPP_MSM_GMIN, read once per C-ABI call by the engine)
+// The range of the tuning members the pipeline is built for; every caller of msm_plan / msm_plan_batch that takes them from outside checks it first.
+//   c:    4 .. 13, the widths msm_plan itself chooses from.  Below 4 an unsplit scalar has more than 64 windows (255 / 3 = 85), and the finish copies one window per
+//         lane of its 64 into the 64 entries of ms.win (k_msm_finish[_vm]); above 13 nb exceeds the 8192 LDS counters of the sort (k_msm_hist_lds /
+//         k_msm_scatter_lds; msm_batch_dev has no other sort) and k_msm_scan's 8 counters per lane, from 17 a digit no longer fits its uint16_t.
+//   ch, gmin: 1 .. 65536.  Larger values have no use (a slot of 2^16 terms is one lane's chain of 2^16 additions) and wrap the 32-bit `hist + ch - 1` and `gmin * stride`.
+inline bool msm_tune_ok(const MsmTune& t) {
+    return (t.c == 0 || (t.c >= 4 && t.c <= 13)) && t.ch <= 65536u && t.gmin <= 65536u;
+}
 inline MsmPlan msm_plan(size_t nreal, int split = 1, const MsmTune& tune = MsmTune()) {
     const size_t n = (size_t)split * nreal;
     int lg = 0; while (((size_t)1 << (lg + 1)) <= n) ++lg;

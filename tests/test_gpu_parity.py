@@ -181,6 +181,57 @@ def test_msm_sort_and_two_stream_forms_vs_oracle(engine, orc, n):
             for k in env: del os.environ[k]
 
 
+MSM_TUNE_CORNERS = [{"RIPP_MSM_C": c, "RIPP_MSM_CH": ch, "RIPP_MSM_GMIN": g} for c in ("4", "13") for ch in ("1", "4") for g in ("1", "16")]
+
+
+@pytest.fixture(scope="module")
+def msm_tune_inputs(engine, orc):
+    """n = 1024 bases of both groups with random and with all-equal scalars, and the oracle's four sums (computed once for all the corners)"""
+    n = 1024
+    s = orc.gen_scalars(61, n); b1, b2 = orc.gen_g1(62, n), orc.gen_g2(63, n)
+    same = np.repeat(orc.fr_array([0x1234567890ABCDEF1234567890ABCDEF1234567890ABCDEF % orc.R]), n, axis=0)
+    exp = {(1, "random"): orc.g1_to_affine(orc.msm_g1_a(b1, s)).reshape(1, 12), (1, "equal"): orc.g1_to_affine(orc.msm_g1_a(b1, same)).reshape(1, 12),
+           (2, "random"): orc.g2_to_affine(orc.msm_g2_a(b2, s)).reshape(1, 24), (2, "equal"): orc.g2_to_affine(orc.msm_g2_a(b2, same)).reshape(1, 24)}
+    return b1, b2, {"random": s, "equal": same}, exp
+
+
+@pytest.mark.parametrize("no_vm", [0, 1])
+@pytest.mark.parametrize("tune", MSM_TUNE_CORNERS, ids=["c%s-ch%s-gmin%s" % (t["RIPP_MSM_C"], t["RIPP_MSM_CH"], t["RIPP_MSM_GMIN"]) for t in MSM_TUNE_CORNERS])
+def test_msm_tuning_corners_vs_oracle(engine, orc, msm_tune_inputs, tune, no_vm):
+    """The in-range corners of the public tuning members (ripp_config.msm_c / msm_ch / msm_gmin, here through the environment) on a single MSM of both groups:
+    c = 4 (32 / 16 windows of 16 buckets) and c = 13 (8192 buckets: the whole LDS counter array of the sort, 8 counters per lane of the scan), slots of 1 and
+    4 terms, grouping from 2 and from 17 slots.  CH = 4, GMIN = 1 with all-equal scalars puts 256 and more slots into one bucket per window, so all three
+    grouping passes run.  Once more under RIPP_NO_VM (the single-lane Jacobian twins of every stage behind the gather)."""
+    import os
+    b1, b2, scalars, exp = msm_tune_inputs
+    env = dict(tune, **({"RIPP_NO_VM": "1"} if no_vm else {}))
+    os.environ.update(env)
+    try:
+        for kind, s in scalars.items():
+            assert np.array_equal(engine.normalize_batch_g1(engine.MultiexponentiationInnerProductG1.inner_product(orc.to_jac_g1(b1), s)), exp[(1, kind)]), (env, "G1", kind)
+            assert np.array_equal(engine.normalize_batch_g2(engine.MultiexponentiationInnerProductG2.inner_product(orc.to_jac_g2(b2), s)), exp[(2, kind)]), (env, "G2", kind)
+    finally:
+        for k in env: del os.environ[k]
+
+
+@pytest.mark.parametrize("c", ["3", "14"])
+def test_msm_tuning_outside_the_range_is_refused(engine, orc, c):
+    """RIPP_MSM_C = 3 would give an unsplit scalar 85 windows (the finish has 64 lanes and entries), 14 gives 16384 buckets (more than the sort's LDS
+    counters): msm_tune_ok (msm.hpp, tests/test_msm_plan_cpu.py) refuses both before anything is allocated or
+    launched, the call returns the argument error, and the next call without the variable is the oracle's sum."""
+    import os
+    n = 64
+    s = orc.gen_scalars(71, n); b1, b2 = orc.gen_g1(72, n), orc.gen_g2(73, n)
+    os.environ["RIPP_MSM_C"] = c
+    try:
+        with pytest.raises(ValueError, match="RIPP_MSM_C"): engine.MultiexponentiationInnerProductG1.inner_product(orc.to_jac_g1(b1), s)
+        with pytest.raises(ValueError, match="RIPP_MSM_C"): engine.MultiexponentiationInnerProductG2.inner_product(orc.to_jac_g2(b2), s)
+    finally:
+        del os.environ["RIPP_MSM_C"]
+    assert np.array_equal(engine.normalize_batch_g1(engine.MultiexponentiationInnerProductG1.inner_product(orc.to_jac_g1(b1), s)), orc.g1_to_affine(orc.msm_g1_a(b1, s)).reshape(1, 12))
+    assert np.array_equal(engine.normalize_batch_g2(engine.MultiexponentiationInnerProductG2.inner_product(orc.to_jac_g2(b2), s)), orc.g2_to_affine(orc.msm_g2_a(b2, s)).reshape(1, 24))
+
+
 def _fr_ints(orc, limbs):
     """(n, 4) Montgomery limbs -> integers, in one pass over the bytes"""
     rinv = pow(1 << 256, -1, orc.R)

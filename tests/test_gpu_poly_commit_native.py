@@ -122,6 +122,50 @@ def test_batch_msm_infinity_and_repeated_bases(engine, orc, N, rows, cols):
         assert _same_g1(orc, got, np.stack([orc.msm_g1_a(np.ascontiguousarray(bases), np.ascontiguousarray(sc[r])) for r in range(rows)]))
 
 
+@pytest.fixture(scope="module")
+def batch_tune_inputs(engine, orc):
+    """3 rows over 256 bases, random and all-equal scalars, with the oracle's points (computed once for all the corners)"""
+    rows, cols = 3, 256
+    bases = engine.synth_g1(515, cols)
+    rnd = engine.synth_fr(516, rows * cols).reshape(rows, cols, 4).copy()
+    same = np.broadcast_to(rnd[0, 0], (rows, cols, 4)).copy()
+    exp = {k: np.stack([orc.msm_g1_a(np.ascontiguousarray(bases), np.ascontiguousarray(sc[r])) for r in range(rows)]) for k, sc in (("random", rnd), ("equal", same))}
+    return bases, {"random": rnd, "equal": same}, exp
+
+
+@pytest.mark.parametrize("c", ["4", "13"])
+@pytest.mark.parametrize("ch", ["1", "4"])
+@pytest.mark.parametrize("gmin", ["1", "16"])
+def test_batch_msm_tuning_corners_vs_oracle(engine, orc, N, batch_tune_inputs, c, ch, gmin):
+    """the in-range corners of ripp_config.msm_c / msm_ch / msm_gmin on the batched pipeline (msm_batch_dev: rows x windows virtual windows through the same
+    stages), against the oracle; all-equal scalars with CH = 4, GMIN = 1 put 128 slots into one bucket, so the grouping passes run over virtual windows"""
+    bases, scalars, exp = batch_tune_inputs
+    env = {"RIPP_MSM_C": c, "RIPP_MSM_CH": ch, "RIPP_MSM_GMIN": gmin}
+    os.environ.update(env)
+    try:
+        for kind, sc in scalars.items():
+            got = N.msm_g1_batch(bases, sc)
+            assert N.msm_batch_chunks() == 1, (env, kind)                                   # the batched pipeline, not the per-row loop
+            assert _same_g1(orc, got, exp[kind]), (env, kind)
+    finally:
+        for k in env: del os.environ[k]
+
+
+@pytest.mark.parametrize("c", ["3", "14"])
+def test_batch_msm_tuning_outside_the_range_is_refused(engine, orc, N, c):
+    """msm_batch_dev has no sort but the one through the 8192 LDS counters: RIPP_MSM_C = 14 (and 3, with the single MSM) is refused by msm_tune_ok before anything is
+    allocated or launched; the next call without the variable gives the loop's points"""
+    rows, cols = 3, 64
+    bases = engine.synth_g1(517, cols); sc = engine.synth_fr(518, rows * cols).reshape(rows, cols, 4).copy()
+    os.environ["RIPP_MSM_C"] = c
+    try:
+        with pytest.raises(ValueError, match="RIPP_MSM_C"): N.msm_g1_batch(bases, sc)
+    finally:
+        del os.environ["RIPP_MSM_C"]
+    got = N.msm_g1_batch(bases, sc)
+    assert _same_g1(orc, got, np.stack([orc.msm_g1_a(np.ascontiguousarray(bases), np.ascontiguousarray(sc[r])) for r in range(rows)]))
+
+
 def test_batch_msm_forced_chunking_gives_the_same_points(engine, orc, N):
     """a low ripp_config.mem_cap_bytes cuts the rows into chunks; the legacy switches select the per-row loop"""
     rows, cols = 64, 16384
